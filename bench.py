@@ -15,8 +15,12 @@ flattened jointly into the FaFp MLPs, latent_dim 8, net [64,64,32], aug
 weekly RK4 steps (dt = 1 week, the longest training curriculum of run_ode.py
 :147-152, gamma = 56).  Synthetic inputs, default nn.Linear init, seed 0.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs when
+--dump-outputs is given, and prints the result line.  --full adds the other lines after it: the
+extra workloads / solvers / loss heads, the strong-scaling companion (N > 1) and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -169,9 +173,11 @@ def one_step(pkg, udist, mod, y0, t, dlat, world):
     torch.autograd.backward(outs, cots)
     if world > 1:
         mod._ude_reducer.finish()
+    return outs
 
 
-def time_steps(pkg, udist, mod, y0, t, dlat, world, steps, warmup, barrier, dev):
+def time_steps(pkg, udist, mod, y0, t, dlat, world, steps, warmup, barrier, dev, keep=None):
+    """keep: a dict that receives the last timed step's outputs (--dump-outputs)."""
     from ude_amd import fused
     for _ in range(warmup):
         one_step(pkg, udist, mod, y0, t, dlat, world)
@@ -179,18 +185,64 @@ def time_steps(pkg, udist, mod, y0, t, dlat, world, steps, warmup, barrier, dev)
     fused.EVENTS = [] if dev.type == "cuda" else None
     barrier()
     _sync(dev)
+    outs = None
     t0 = time.perf_counter()
     for _ in range(steps):
-        one_step(pkg, udist, mod, y0, t, dlat, world)
+        outs = one_step(pkg, udist, mod, y0, t, dlat, world)
+        if keep is None:
+            outs = None                          # not dumping: a step's outputs are freed when it returns
     barrier()
     _sync(dev)
     el = time.perf_counter() - t0
     evs = fused.EVENTS or []
     fused.EVENTS = None
+    if keep is not None:
+        keep["outs"] = outs
     k_ms = {"fwd": [], "bwd": []}
     for kind, e0, e1 in evs:
         k_ms[kind].append(e0.elapsed_time(e1))
     return el, {k: (sum(v) / len(v) if v else None) for k, v in k_ms.items()}
+
+
+DUMP_ARRAY_BYTES = 16 << 20     # a larger per-trajectory array is dumped as a sample of trajectories
+DUMP_TOTAL_BYTES = 64 << 20
+
+
+def dump_outputs(path, mod, y0, outs):
+    """--dump-outputs: what the last timed step handed its caller -- the latent at every grid point,
+    the posterior mean / std and |Fa| (where the model has them), d y0 and every parameter gradient --
+    as <path>/<name>.npy (float32).  The latent and d y0 are written for a fixed sample of the
+    trajectories (seed 0, ascending, the same indices for both) when the whole array would exceed
+    DUMP_ARRAY_BYTES; the sampling depends on the shapes alone, so two builds write the same entries."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    names = ["latent"]
+    if mod.ode_type in ("Fp", "FaFp"):
+        names += ["posterior_mean", "posterior_std"]
+    if mod.ode_type in ("Fa", "FaFp"):
+        names.append("fa_norm")
+    arrays = dict(zip(names, outs, strict=True))
+    arrays["grad_y0"] = y0.grad
+    for name, p in mod.named_parameters():
+        if p.grad is not None:
+            arrays["grad_" + name] = p.grad
+    n_traj = y0.shape[0]
+    per_traj = max(arrays["latent"][:, 0].numel(), y0[0].numel()) * 4
+    idx = None
+    if per_traj * n_traj > DUMP_ARRAY_BYTES:
+        k = max(DUMP_ARRAY_BYTES // per_traj, 1)
+        idx = torch.from_numpy(np.sort(np.random.default_rng(0).choice(n_traj, size=k, replace=False)))
+    total = 0
+    for name, a in arrays.items():
+        a = a.detach()
+        if idx is not None and name in ("latent", "grad_y0"):
+            a = a.index_select(1 if name == "latent" else 0, idx.to(a.device))
+        a = a.to("cpu", torch.float32).contiguous().numpy()
+        total += a.nbytes
+        if total > DUMP_TOTAL_BYTES:
+            raise SystemExit(f"--dump-outputs: {name} takes the dump past {DUMP_TOTAL_BYTES} bytes")
+        np.save(os.path.join(path, name.replace("/", "_") + ".npy"), a)
+    print(f"[bench] wrote {len(arrays)} arrays ({total / 2**20:.1f} MiB) to {path}", file=sys.stderr, flush=True)
 
 
 # host threads of the CPU baseline: the GPU box's CPU share per GPU (OMP_NUM_THREADS there)
@@ -479,13 +531,17 @@ def _sync(dev):
         torch.cuda.synchronize(dev)
 
 
-def measure(pkg, udist, w, n_traj, dev, rank, world, steps, warmup, barrier):
+def measure(pkg, udist, w, n_traj, dev, rank, world, steps, warmup, barrier, dump=None):
     """Time `steps` fwd+bwd steps of workload w with n_traj trajectories on this rank;
-    returns (max-over-ranks seconds, HIP-event kernel averages)."""
+    returns (max-over-ranks seconds, HIP-event kernel averages).  dump: directory that receives
+    rank 0's outputs of the last timed step (dump_outputs)."""
     import torch.distributed as dist
     w = dict(w, n_traj=n_traj)
     mod, y0, t, dlat = build(pkg, w, dev, seed=1000 + rank)
-    el, kms = time_steps(pkg, udist, mod, y0, t, dlat, world, steps, warmup, barrier, dev)
+    keep = {} if dump and rank == 0 else None
+    el, kms = time_steps(pkg, udist, mod, y0, t, dlat, world, steps, warmup, barrier, dev, keep)
+    if keep is not None:
+        dump_outputs(dump, mod, y0, keep.pop("outs"))
     if world > 1:
         x = torch.tensor([el], device=dev, dtype=torch.float64)
         dist.all_reduce(x, op=dist.ReduceOp.MAX)
@@ -497,7 +553,10 @@ def time_steps_graphed(pkg, udist, mod, y0, t, dlat, steps, warmup, dev):
     """The same step replayed as a HIP graph (ude_amd/graphs.py GraphedStep: the pack, the fused
     forward, the backward and its tail, the gradient accumulation -- one host call per step)."""
     from ude_amd.graphs import GraphedStep
-    gs = GraphedStep(lambda: one_step(pkg, udist, mod, y0, t, dlat, 1), warmup=max(warmup, 1))
+    def step():                                   # returns nothing: the graph holds no step outputs
+        one_step(pkg, udist, mod, y0, t, dlat, 1)
+
+    gs = GraphedStep(step, warmup=max(warmup, 1))
     for _ in range(max(warmup, 1)):
         gs.replay()
     _sync(dev)
@@ -545,13 +604,25 @@ def main():
                     help="weak: every rank solves the workload's batch; strong: the batch is split over ranks")
     ap.add_argument("--n-traj", type=int, default=None,
                     help="development: override the workload's trajectory count (not a benchmark line)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true")
-    ap.add_argument("--lines", default=None, help="comma-separated subset of the extra lines (development)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline: the extra lines (other workloads, solvers, loss heads), the "
+                         "strong-scaling companion (N > 1) and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (latent, posterior mean / std, |Fa|, d y0, "
+                         "parameter gradients) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-extra", action="store_true",
+                    help="with --full: skip the extra lines and the strong-scaling companion")
+    ap.add_argument("--lines", default=None,
+                    help="with --full: comma-separated subset of the extra lines (development)")
     ap.add_argument("--dist-backend", default="nccl", help="nccl (= RCCL) for runs; gloo only to rehearse N>1")
     ap.add_argument("--rehearse-cpu", action="store_true",
                     help="plumbing rehearsal on the host (gloo, eager solver): checks ranks / batch accounting")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    extras = args.full and not args.no_extra
+    cpu_lines = args.full and not args.no_cpu_baseline
 
     world_env = os.environ.get("WORLD_SIZE")
     if world_env is None and args.gpus > 1:
@@ -592,7 +663,8 @@ def main():
     per_rank = w["n_traj"] if args.scaling == "weak" else w["n_traj"] // world
     if args.scaling == "strong" and per_rank * world != w["n_traj"]:
         raise SystemExit(f"strong scaling: {w['n_traj']} trajectories do not split over {world} ranks")
-    el, kms, mod, n_steps_rk = measure(pkg, udist, w, per_rank, dev, rank, world, args.steps, args.warmup, barrier)
+    el, kms, mod, n_steps_rk = measure(pkg, udist, w, per_rank, dev, rank, world, args.steps, args.warmup, barrier,
+                                       dump=args.dump_outputs)
     units = world * per_rank * n_steps_rk * args.steps
     value = units / el
     macs = macs_per_eval(w)
@@ -602,7 +674,7 @@ def main():
 
     # strong-scaling companion (N > 1, weak headline): the same global batch split over the ranks
     strong = None
-    if world > 1 and args.scaling == "weak" and not args.no_extra and w["n_traj"] % world == 0:
+    if world > 1 and args.scaling == "weak" and extras and w["n_traj"] % world == 0:
         el_s, kms_s, _, _ = measure(pkg, udist, w, w["n_traj"] // world, dev, rank, world, args.steps,
                                     args.warmup, barrier)
         strong = {"scaling": "strong", "global_batch": w["n_traj"], "traj_per_gpu": w["n_traj"] // world,
@@ -645,7 +717,7 @@ def main():
         }
         if strong is not None:
             res["strong_scaling"] = strong
-    extra = rank == 0 and world == 1 and not args.no_extra and args.workload == "state49" and not args.rehearse_cpu
+    extra = rank == 0 and world == 1 and extras and args.workload == "state49" and not args.rehearse_cpu
     if extra:
         lines = [("north_star_M1", lambda: dict(extra_line(pkg, udist, "us_northstar", dev, barrier),
                                                 target_rhs_evals_per_s=1e7)),
@@ -669,7 +741,7 @@ def main():
             res[name] = fn()
             torch.cuda.empty_cache()
             print(f"[bench] {name}: {time.perf_counter() - t0:.1f} s", file=sys.stderr, flush=True)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline and not args.rehearse_cpu:
+    if rank == 0 and world == 1 and cpu_lines and not args.rehearse_cpu:
         print("[bench] cpu baselines", file=sys.stderr, flush=True)
         res["cpu_baseline"] = cpu_baseline(w, mod, threads=CPU_THREADS)
         res["cpu_baseline_1thread"] = cpu_baseline(w, mod, threads=1)

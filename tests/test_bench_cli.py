@@ -19,7 +19,7 @@ def _run(args, env_extra=None):
 
 def test_bench_launches_ranks_and_accounts_batch():
     r = _run(["--gpus", "2", "--steps", "1", "--warmup", "0", "--rehearse-cpu", "--workload", "tiny",
-              "--no-cpu-baseline"])
+              "--full", "--no-cpu-baseline"])
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout                       # rank 0 only prints
@@ -45,3 +45,22 @@ def test_bench_refuses_world_size_mismatch():
               "--no-cpu-baseline"], {"WORLD_SIZE": "1", "RANK": "0", "LOCAL_RANK": "0"})
     assert r.returncode != 0
     assert "WORLD_SIZE" in r.stderr
+
+
+def test_bench_plain_run_is_headline_only_and_dumps_outputs(tmp_path):
+    """A plain run prints the headline line alone (the companion, extra and CPU-baseline lines are --full's)
+    and --dump-outputs writes the last timed step's outputs as float32 .npy files."""
+    import numpy as np
+    out = tmp_path / "dump"
+    r = _run(["--gpus", "1", "--steps", "2", "--warmup", "1", "--rehearse-cpu", "--workload", "tiny",
+              "--dump-outputs", str(out)])
+    assert r.returncode == 0, r.stderr[-3000:]
+    res = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][0])
+    assert res["steps"] == 2 and res["ms_per_step"] > 0 and res["dtype"] == "f32"
+    assert abs(res["value"] - 64 * 4 / (res["ms_per_step"] * 1e-3)) <= 1e-6 * res["value"]
+    assert not [k for k in res if k.startswith("cpu_baseline") or k == "strong_scaling"]
+    got = {p.stem: np.load(p) for p in out.glob("*.npy")}
+    assert {"latent", "posterior_mean", "posterior_std", "fa_norm", "grad_y0", "grad_net.1.weight"} <= set(got)
+    assert got["latent"].shape == (5, 64, 1, 8) and got["grad_y0"].shape == (64, 1, 8)
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in got.values())
+    assert sum(a.nbytes for a in got.values()) <= 64 << 20

@@ -11,5 +11,5 @@ grep -E "^FAILED|Error" $OUT/pytest_gpu.log | head -20
 [ $rc -ne 0 ] && exit $rc
 timeout -k 10 200 python -u tools/step_ops.py > $OUT/step_ops.txt 2>&1 || exit 31
 grep -E "device activities" $OUT/step_ops.txt
-timeout -k 10 400 python -u bench.py --steps 20 --warmup 5 --lines $LINES --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit $?
+timeout -k 10 400 python -u bench.py --full --steps 20 --warmup 5 --lines $LINES --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err || exit $?
 python3 tools/bench_summary.py $OUT/bench.json

@@ -7,7 +7,7 @@ R=$(pwd)
 OUT=${OUT:-gpurun_out/measure}
 mkdir -p $OUT
 O=$R/$OUT
-timeout -k 10 600 python -u bench.py --steps 10 --warmup 3 > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 21; }
+timeout -k 10 600 python -u bench.py --full --steps 10 --warmup 3 > $O/bench_full.json 2> $O/bench_full.err || { tail -20 $O/bench_full.err; exit 21; }
 python3 tools/bench_summary.py $O/bench_full.json
 B="python3 $R/bench.py --no-extra --no-cpu-baseline"
 cd /tmp
