@@ -34,6 +34,9 @@ bool matches(const UdeModelDesc* d) {
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return UDE_E_HIP; } while (0)
 
+template <class M> struct is_recompute { static constexpr bool value = false; };
+template <class B> struct is_recompute<Recompute<B>> { static constexpr bool value = true; };
+
 template <class M>
 struct Ops {
   static constexpr int DY0_STATIC_LDS = TT * M::R * M::L * 4;
@@ -55,6 +58,14 @@ struct Ops {
                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, M::SPLIT_FWD, true>,
                                hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    // the inference decoder forward (forecast_dec; it stores nothing, so the Recompute view has none)
+    if constexpr (!is_recompute<M>::value) {
+      HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false, false, true>,
+                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+      if constexpr (M::FWD_RES)
+        HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false, false, true, true>,
+                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    }
     HIPCHK(hipFuncSetAttribute((const void*)&ude_dec_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                DecBwdDims<M>::LDS));
     // the static-feature dy0 kernel stages one tile's (16, R, L) time sums of d latent in LDS
@@ -272,6 +283,56 @@ struct Ops {
       HIPCHK(hipGetLastError());
     }
     return UDE_OK;
+  }
+
+  // Inference forward with the decoder epilogue (the forecast): y_hat (T, N, R) and the side statistics;
+  // no latent, checkpoint, stored activations or final-state block.  latent_init_loss is optional
+  // (reg_slab / reg_out both null: skipped).  Dispatch as forward() without a ckpt: the resident-weight
+  // kernel when every tile has a CU of its own, else the plain one (never SPLIT: its extra waves only store).
+  static int forecast_dec(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
+                          const float* dec_pack, float* yhat, double* stats_slab, double* reg_slab,
+                          const UdeSideStats* st, unsigned* ctl, float* reg_out, hipStream_t s) {
+    if constexpr (is_recompute<M>::value) {
+      return UDE_E_UNSUPPORTED;
+    } else {
+    if (!pack || !sched || !y0 || !dec_pack || !yhat || !stats_slab || !stats_ok(st) || (!reg_slab) != (!reg_out))
+      return UDE_E_INVALID;
+    if (p->n_steps < 1) return UDE_E_INVALID;
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    int gf = 1, gb = 1;
+    int rc = grids(dev, n_tiles, &gf, &gb);
+    if (rc) return rc;
+    KArgs a;
+    memset(&a, 0, sizeof(a));
+    a.pack = pack; a.y0 = y0; a.sched = (const unsigned char*)sched;
+    a.stats_slab = stats_slab;
+    a.dec_pack = dec_pack; a.yhat = yhat; a.reg_slab = reg_slab;
+    a.n_traj = p->n_traj; a.n_steps = p->n_steps; a.n_out = p->n_out; a.n_tiles = n_tiles;
+    a.fa_w = p->fa_w;
+    const double n_eval = 4.0 * (double)p->n_steps * (double)p->n_traj * (double)M::R;
+    set_stats_out(a, st, ctl, n_eval);
+    a.o_reg = reg_out;
+    int cus = 0;
+    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
+    const bool res = fwd_res(n_tiles, cus);
+    if (res) gf = n_tiles < cus ? n_tiles : cus;
+    if (res)
+      hipLaunchKernelGGL((ude_fwd_kernel<M, false, false, true, M::FWD_RES>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
+    else hipLaunchKernelGGL((ude_fwd_kernel<M, false, false, true>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
+    HIPCHK(hipGetLastError());
+    if (!ctl) {
+      hipLaunchKernelGGL(ude_stats_finalize_kernel<0>, dim3(1), dim3(320), 0, s, stats_slab, gf, n_eval, a.o_mean,
+                         a.o_std, a.o_norm);
+      HIPCHK(hipGetLastError());
+      if (reg_slab) {
+        hipLaunchKernelGGL(ude_sum_finalize_kernel<0>, dim3(1), dim3(64), 0, s, (const double*)reg_slab, gf, reg_out);
+        HIPCHK(hipGetLastError());
+      }
+    }
+    return UDE_OK;
+    }
   }
 
   // Backward of the decoder epilogue: dl3 (T, N, R, 3) for ude_rk4_backward_sir, d W_dec, d b_dec.
@@ -894,6 +955,8 @@ struct Entry {
   int (*nll_backward)(int, int, int, const float*, const float*, const float*, const void*, float*, hipStream_t);
   int (*rhs_eval_vjp)(const UdeProblem*, const float*, const float*, const float*, float*, float, float*, void*,
                       float*, hipStream_t);
+  int (*forecast_dec)(const UdeProblem*, const float*, const void*, const float*, const float*, float*, double*,
+                      double*, const UdeSideStats*, unsigned*, float*, hipStream_t);
 };
 
 template <class M>
@@ -902,7 +965,8 @@ constexpr Entry make_entry() {
                &DopriOps<M>::workspace, &DopriOps<M>::forward, &LossOps<M>::workspace, &LossOps<M>::forward,
                &LossOps<M>::backward, &LossOps<M>::backward_sir, &EvalOps<M>::workspace, &EvalOps<M>::forward,
                &EvalOps<M>::vjp, &Ops<M>::dec_pack, &Ops<M>::forward_dec, &Ops<M>::dec_backward,
-               &Ops<M>::nll_workspace, &Ops<M>::nll_forward, &Ops<M>::nll_backward, &EvalOps<M>::fused};
+               &Ops<M>::nll_workspace, &Ops<M>::nll_forward, &Ops<M>::nll_backward, &EvalOps<M>::fused,
+               &Ops<M>::forecast_dec};
 }
 
 

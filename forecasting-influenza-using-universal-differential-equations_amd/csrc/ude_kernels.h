@@ -760,7 +760,8 @@ __device__ __forceinline__ void publish_fence() {
   __asm__ __volatile__("" ::: "memory");           // and the compiler keeps every access on its side
 }
 
-template <bool DEC>
+// OPT (the inference DEC forward): the latent_init_loss buffers are optional, null skips the term
+template <bool DEC, bool OPT = false>
 __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
   publish_fence();
   unsigned int ticket = 0;
@@ -773,7 +774,10 @@ __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
 #pragma unroll
   for (int c = 0; c < 5; ++c) tot[c] = wave_sum_partials(A.stats_slab, ng, 5, c, ln);
   double reg = 0.0;
-  if constexpr (DEC) reg = wave_sum_partials(A.reg_slab, ng, 1, 0, ln);
+  const bool has_reg = DEC && (!OPT || (A.reg_slab && A.o_reg));
+  if constexpr (DEC) {
+    if (has_reg) reg = wave_sum_partials(A.reg_slab, ng, 1, 0, ln);
+  }
   if (ln < 2) {
     const double n = A.n_eval, t0 = ln == 0 ? tot[0] : tot[1], t2 = ln == 0 ? tot[2] : tot[3];
     const double m = t0 / n;
@@ -782,7 +786,7 @@ __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
     if (A.o_std) A.o_std[ln] = (float)sqrt(var > 0.0 ? var : 0.0);
   }
   if (ln == 2 && A.o_norm) A.o_norm[0] = (float)sqrt(tot[4]);
-  if (ln == 3 && DEC) A.o_reg[0] = (float)reg;
+  if (ln == 3 && has_reg) A.o_reg[0] = (float)reg;
   if (A.o_sums && ln < 5) {
     double v = tot[0];
 #pragma unroll
@@ -1128,7 +1132,8 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
     for (int c = 0; c < NS; ++c) red[(tid >> 6) * NS + c] = v[c];
   }
   lds_sync();
-  if (tid < NS) {
+  // the inference DEC forward (!TRAIN): latent_init_loss is optional (null reg_slab: skipped)
+  if (tid < NS && (TRAIN || tid < 5 || A.reg_slab)) {
     double s = 0;
     for (int w = 0; w < WAVES; ++w) s += red[w * NS + tid];
     double* dst = tid < 5 ? A.stats_slab + (size_t)blockIdx.x * 5 + tid : A.reg_slab + blockIdx.x;
@@ -1139,7 +1144,7 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
   }
   // the last workgroup to finish turns every workgroup's partials into the statistics (no separate
   // finalize launch; wave 0 only, so the split forward's partner waves keep their barrier sequence)
-  if (A.ctl && tid < 64) finalize_stats_last<DEC>(A, tid);
+  if (A.ctl && tid < 64) finalize_stats_last<DEC, DEC && !TRAIN>(A, tid);
 #ifdef UDE_PROFILE
   if (pf) for (int i = 0; i < NPROF; ++i) A.prof[(size_t)blockIdx.x * NPROF + i] = prof_.acc[i];
 #endif

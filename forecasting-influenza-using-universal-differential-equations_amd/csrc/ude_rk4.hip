@@ -5,6 +5,7 @@
 #include "ude_rk4.h"
 #include "ude_entry.h"
 #include "ude_vec.h"      // model-independent vector kernels (compiled in both passes)
+#include "ude_forecast.h" // model-independent ensemble summary kernels (likewise)
 
 // This translation unit is host code only (no kernels are instantiated here).
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -280,6 +281,27 @@ int ude_nll_backward(const UdeModelDesc* m, int32_t T, int32_t S, int32_t B, con
   const Entry* e = find(m);
   if (!e) return UDE_E_UNSUPPORTED;
   return e->nll_backward(T, S, B, yhat, y, grad, ws, dyhat, (hipStream_t)stream);
+}
+
+int ude_rk4_forecast_dec(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,
+                         const float* y0, const float* dec_pack, float* yhat, double* stats_slab, uint32_t* ctl,
+                         const UdeSideStats* stats, ude_stream_t stream) {
+  const Entry* e = find(m);
+  if (!e) return UDE_E_UNSUPPORTED;
+  if (!p || p->n_traj < 1 || p->n_steps < 1 || !stats) return UDE_E_INVALID;
+  return e->forecast_dec(p, pack, sched, y0, dec_pack, yhat, stats_slab, nullptr, stats, ctl, nullptr,
+                         (hipStream_t)stream);
+}
+
+int ude_forecast_summary_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int64_t* ws_bytes) {
+  return ude::forecast_summary_workspace(T, S, B, R, n_q, ws_bytes);
+}
+
+int ude_forecast_summary(int32_t T, int32_t S, int32_t B, int32_t R, const float* yhat, const double* scale,
+                         const float* y_true, const double* q, int32_t n_q, void* ws, double* mean, double* std,
+                         double* quant, double* scores, ude_stream_t stream) {
+  return ude::forecast_summary(T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, scores,
+                               (hipStream_t)stream);
 }
 
 #ifdef UDE_PROFILE

@@ -24,6 +24,9 @@ Bayesian RHS (models_bayes.py, run_ode.py's ``*b`` models) takes the same epilog
 the epilogue does not apply (output times between grid points, a non-reference decoder) the latent
 is written and the fused loss head (ude_amd/loss_head.py: decoder + nll_loss + latent_init_loss in
 one kernel pass each) serves the same terms.
+``VAE.forecast`` is the forecast side (``evaluate``, ``train(validate=...)``, lib/utils.py ``test``
+on a HIP device): the inference solve with the decoder epilogue and the ensemble summary kernels
+(ude_amd/forecast.py) -- no latent, no checkpoint, only the summary copied to the host.
 """
 from itertools import chain
 
@@ -40,6 +43,7 @@ import lib.train_functions as train_functions
 from lib.in_development.models_bayes import Dense_Variational
 from ude_amd import decoder_head
 from ude_amd import distributed as udist
+from ude_amd import forecast as ude_forecast
 from ude_amd import loss_head
 
 
@@ -56,7 +60,16 @@ def _scale_forecast(y_pred, y_test, scaler):
     return y_pred.detach().cpu().numpy() * s[None, None, None, :], y_test.detach().cpu().numpy() * s[None, None, :]
 
 
+def _on_hip(model):
+    return torch.device(getattr(model, "device", "cpu")).type == "cuda" and hasattr(model, "forecast")
+
+
 def evaluate(model, x_test, y_test, t, scaler, n_samples=128):
+    if _on_hip(model):
+        # on a HIP device: the fused forecast, scored on the device (only the (T,) scores come back)
+        nll = model.forecast(x_test, t, n_samples=n_samples, y_true=y_test, scaler=scaler).nll.cpu().numpy()
+        nlls = [nll[g] for g in range(57)]
+        return {"forecast_nll": np.mean(nlls[-28:]), "all_nll": np.mean(nlls)}
     y_pr, y_te = _scale_forecast(model(x_test, t, n_samples=n_samples), y_test, scaler)
     mu, sd = y_pr.mean(1), y_pr.std(1)
     nlls = [Metrics.nll(y_te[:, g, :], mu[:, g, :], sd[:, g, :]) for g in range(57)]
@@ -196,6 +209,46 @@ class VAE:
         # calc_loss may take nll / reg from the fused loss head when handed this prediction
         self._pred_src = (y_pred, n_samples, B, None, None) if training else None
         return y_pred
+
+    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None):
+        """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
+        (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
+        by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
+        ``quantiles``, and with targets ``y_true`` (B, T, R) the per-day Metrics nll / skill / mae).
+        The draw is ``__call__``'s: one ``torch.randn(n_samples, B, R, ld_enc)``, the same encoding
+        and reparameterisation, under ``torch.no_grad()``.  On a HIP device with an eligible model the
+        inference solve's decoder epilogue emits the prediction (no latent, no checkpoint) and the
+        summary kernels read it once: nothing but the summary is copied to the host, and
+        ``self.latent`` is None afterwards.  Otherwise ``__call__(training=False)`` is summarised."""
+        B = x.shape[0]
+        dev_is_hip = torch.device(self.device).type == "cuda"
+        lin = decoder_head.decoder_linear(self.dec)
+        if dev_is_hip and lin is not None and self._dp_eps is None:
+            self.__dict__["_latent"] = None
+            self._pred_src = None
+            eps = torch.randn(n_samples, B, self.n_regions, self.ld_enc, dtype=self.dtype, device=self.device)
+            self.ode.clear_tracking()
+            with torch.no_grad():
+                if self.uncertainty:
+                    self.mean, self.std = self.enc(x)
+                    z = models.reparam(eps, self.std, self.mean, n_samples, B, uncertainty=True) + 1e-5
+                else:
+                    n_samples = 1
+                    self.mean = self.enc(x)
+                    z = (models.reparam(eps, None, self.mean, n_samples, B, uncertainty=False) + 1e-5).unsqueeze(1)
+                yhat = ude_forecast.solve_decode_forecast(self.ode, z, t, t[1] - t[0], lin)
+                if yhat is None:
+                    # not eligible (output times between grid points, an RHS without a kernel): the
+                    # latent path on the same draw
+                    self.latent = odeint(self.ode, z, t, method="rk4", options=dict(step_size=t[1] - t[0]))
+                    yhat = self.dec(self.latent[..., :3]).reshape(len(t), n_samples * B, self.n_regions)
+            return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler,
+                                                 quantiles=quantiles)
+        y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
+        if not self.uncertainty:
+            n_samples = 1
+        yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
+        return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles)
 
     def _fused_head(self, y_pred, y_true, losses):
         """(nll, reg, per-group prediction mean / std) for this model's latest training prediction:
@@ -389,7 +442,14 @@ class VAE:
             if sched is not None:
                 sched.step()
             self._history.reset()
-            if validate is not None:
+            if validate is not None and _on_hip(self):
+                nll = self.forecast(validate["x_test"], validate["t"], n_samples=validate["n_samples"],
+                                    y_true=validate["y_test"], scaler=validate["scaler"]).nll.cpu().numpy()
+                # the reference scores range(len(t)) with the TRAINING grid t (ref lib/VAE.py:278)
+                nlls = [nll[g] for g in range(len(t))]
+                self._history.epoch_history[-1]["forecast_nll"] = np.mean(nlls[-28:])
+                self._history.epoch_history[-1]["all_nll"] = np.mean(nlls)
+            elif validate is not None:
                 y_pred = self(validate["x_test"], validate["t"], n_samples=validate["n_samples"], training=False)
                 y_pr, y_te = _scale_forecast(y_pred, validate["y_test"], validate["scaler"])
                 mu, sd = y_pr.mean(1), y_pr.std(1)

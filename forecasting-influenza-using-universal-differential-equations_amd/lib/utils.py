@@ -3,6 +3,7 @@ init_network_weights :69-73, update_learning_rate :75-79, make_file :81-84)."""
 import os
 
 import numpy as np
+import torch
 import torch.nn as nn
 
 import lib.Metrics as Metrics
@@ -17,16 +18,26 @@ def test(model, scaler, x_test, y_test, t, test_season, window_size=1, variables
     """Forward-only forecast of the test windows at n_samples MC samples (run_ode.py:166 calls it
     with 128), scored per horizon (7/14/21/28 days after the window) with Metrics.nll / skill
     into ``<file_name>.csv`` under a FileLock: the row whose ``variables`` all match is updated,
-    else a new row is appended.  The forecast runs wherever the model lives (the fused solve on
-    a HIP device); the scoring reads it back to the host."""
+    else a new row is appended.  A model on a HIP device forecasts and scores there
+    (``VAE.forecast``); a CPU model is scored on the host as in the reference."""
     import pandas as pd
     from filelock import FileLock
-    y_pred = model(x_test, t, n_samples=n_samples, training=False)
-    s = scaler.values if hasattr(scaler, "values") else np.asarray(scaler)
-    y_pr = _np(y_pred) * s[np.newaxis, np.newaxis, np.newaxis, :]
-    y_te = _np(y_test) * s[np.newaxis, np.newaxis, :]
-    pred_mean = y_pr.mean(1)
-    pred_std = y_pr.std(1)
+    horizons = [window_size + 6, window_size + 13, window_size + 20, window_size + 27]
+    if torch.device(getattr(model, "device", "cpu")).type == "cuda" and hasattr(model, "forecast"):
+        # on a HIP device: the fused forecast (inference solve with the decoder epilogue + the summary
+        # kernels); only the per-day scores come back to the host
+        fc = model.forecast(x_test, t, n_samples=n_samples, y_true=y_test, scaler=scaler)
+        nll_t, skill_t = fc.nll.cpu().numpy(), fc.skill.cpu().numpy()
+        score = lambda g: (nll_t[g], skill_t[g])
+    else:
+        y_pred = model(x_test, t, n_samples=n_samples, training=False)
+        s = scaler.values if hasattr(scaler, "values") else np.asarray(scaler)
+        y_pr = _np(y_pred) * s[np.newaxis, np.newaxis, np.newaxis, :]
+        y_te = _np(y_test) * s[np.newaxis, np.newaxis, :]
+        pred_mean = y_pr.mean(1)
+        pred_std = y_pr.std(1)
+        score = lambda g: (Metrics.nll(y_te[:, g, :], pred_mean[:, g, :], pred_std[:, g, :]),
+                           Metrics.skill(y_te[:, g, :], pred_mean[:, g, :], pred_std[:, g, :]))
     with FileLock(file_name + ".lock"):
         results_df = pd.read_csv(file_name + ".csv", index_col=0)
         common = None
@@ -41,11 +52,8 @@ def test(model, scaler, x_test, y_test, t, test_season, window_size=1, variables
             row = (np.max(results_df.index) + 1) if len(results_df.index) else 0
         for key, value in variables.items():
             results_df.loc[row, key] = value
-        for col, g in zip([7, 14, 21, 28], [window_size + 6, window_size + 13, window_size + 20, window_size + 27]):
-            results_df.loc[row, f"{test_season} {g}"] = Metrics.nll(y_te[:, g, :], pred_mean[:, g, :],
-                                                                    pred_std[:, g, :])
-            results_df.loc[row, f"skill {test_season} {col}"] = Metrics.skill(y_te[:, g, :], pred_mean[:, g, :],
-                                                                              pred_std[:, g, :])
+        for col, g in zip([7, 14, 21, 28], horizons):
+            results_df.loc[row, f"{test_season} {g}"], results_df.loc[row, f"skill {test_season} {col}"] = score(g)
         results_df.to_csv(file_name + ".csv")
 
 

@@ -44,7 +44,8 @@ EXPORTED_SYMBOLS = ("ude_supported", "ude_query", "ude_pack_weights", "ude_pack_
                     "ude_decoder_backward", "ude_nll_workspace", "ude_nll_forward", "ude_nll_backward",
                     "ude_rhs_eval_vjp", "ude_lincomb", "ude_scaled_sumsq", "ude_build_info",
                     "ude_rk4_forward_ex", "ude_rk4_forward_dec_ex", "ude_rk4_backward_ex", "ude_lincomb_hc",
-                    "ude_dopri_ratio")
+                    "ude_dopri_ratio", "ude_rk4_forecast_dec", "ude_forecast_summary_workspace",
+                    "ude_forecast_summary")
 SUMSQ_WS = 1025          # doubles of ude_scaled_sumsq's output / workspace (UDE_SUMSQ_WS)
 
 
@@ -190,6 +191,13 @@ class NativeLib:
         L.ude_rk4_forward_dec_ex.restype = i32
         L.ude_rk4_backward_ex.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, pst, pdst, vp, vp, vp, vp, vp]
         L.ude_rk4_backward_ex.restype = i32
+        L.ude_rk4_forecast_dec.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, pst, vp]
+        L.ude_rk4_forecast_dec.restype = i32
+        i32s = ctypes.c_int32
+        L.ude_forecast_summary_workspace.argtypes = [i32s, i32s, i32s, i32s, i32s, ctypes.POINTER(ctypes.c_int64)]
+        L.ude_forecast_summary_workspace.restype = i32
+        L.ude_forecast_summary.argtypes = [i32s, i32s, i32s, i32s, vp, vp, vp, vp, i32s, vp, vp, vp, vp, vp, vp]
+        L.ude_forecast_summary.restype = i32
 
     def supported(self, desc: UdeModelDesc) -> bool:
         return bool(self.lib.ude_supported(ctypes.byref(desc)))
@@ -346,6 +354,21 @@ class NativeLib:
     def nll_backward(self, desc, T, S, B, yhat, y, grad, ws, dyhat, stream) -> None:
         check(self.lib.ude_nll_backward(ctypes.byref(desc), int(T), int(S), int(B), yhat, y, grad, ws, dyhat,
                                         stream), "ude_nll_backward")
+
+    def forecast_dec(self, desc, prob, pack, sched, y0, dec_pack, yhat, stats_slab, ctl, stats: UdeSideStats,
+                     stream) -> None:
+        check(self.lib.ude_rk4_forecast_dec(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
+                                            stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forecast_dec")
+
+    def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
+        out = ctypes.c_int64(0)
+        check(self.lib.ude_forecast_summary_workspace(int(T), int(S), int(B), int(R), int(n_q), ctypes.byref(out)),
+              "ude_forecast_summary_workspace")
+        return int(out.value)
+
+    def forecast_summary(self, T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, scores, stream) -> None:
+        check(self.lib.ude_forecast_summary(int(T), int(S), int(B), int(R), yhat, scale, y_true, q, int(n_q), ws,
+                                            mean, std, quant, scores, stream), "ude_forecast_summary")
 
     def build_info(self) -> str:
         return self.lib.ude_build_info().decode()

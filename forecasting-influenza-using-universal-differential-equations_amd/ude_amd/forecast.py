@@ -1,0 +1,240 @@
+"""The ensemble forecast: inference solve with the decoder epilogue + on-device summary.
+
+The reference's forecast side (lib/utils.py:20-56 ``test``, lib/VAE.py ``evaluate`` and the
+``validate=`` branch of ``VAE.train``) solves ``n_samples`` trajectories per test window, decodes
+the whole (T, N, R, L) latent, copies the (B, S, T, R) prediction to the host and forms the
+per-(window, day, region) mean / std with NumPy and the per-horizon scores with SciPy.
+
+``solve_decode_forecast`` is that solve without autograd on the gfx950 kernels
+(ude_rk4_forecast_dec): the forward kernel's decoder epilogue emits ``y_hat (T, N, R) =
+Decoder(latent[..., :3])`` at every output time; no latent, checkpoint or stored activation is
+written.  ``ensemble_summary`` turns ``y_hat`` into a ``Forecast`` (mean, population std, quantiles,
+and against targets the per-day Metrics.nll / skill / mae) in one read of ``y_hat``
+(ude_forecast_summary; fp64 after the load, fixed-order sums: the same bits run to run).  On a CPU
+tensor the same definitions run on torch fp64 operators.
+"""
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass, fields
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _native
+from . import decoder_head
+from . import fused as _fused
+
+MASS_FLOOR = 4.5399929762484854e-05      # lib/Metrics.py mb_log: an exactly zero mass -> e^-10
+MAX_QUANTILE_SAMPLES = 1024              # FC_MAX_SQ (csrc/ude_forecast.h)
+
+
+@dataclass
+class Forecast:
+    """Per-(window, day, region) summary of an ensemble forecast (fp64 tensors on the forecast's
+    device): ``mean`` / ``std`` (B, T, R) (population std, as numpy.std), ``quantiles`` (Q, B, T, R)
+    or None, and -- when targets were given -- ``nll`` / ``skill`` / ``mae`` (T,): lib/Metrics.py's
+    scores of every time index over its B * R groups."""
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: Optional[torch.Tensor] = None
+    nll: Optional[torch.Tensor] = None
+    skill: Optional[torch.Tensor] = None
+    mae: Optional[torch.Tensor] = None
+
+    def _map(self, fn):
+        return Forecast(**{f.name: (None if getattr(self, f.name) is None else fn(getattr(self, f.name)))
+                           for f in fields(self)})
+
+    def cpu(self) -> "Forecast":
+        """One stacked device-to-host copy of every field."""
+        names = [f.name for f in fields(self) if getattr(self, f.name) is not None]
+        parts = [getattr(self, n) for n in names]
+        if not parts[0].is_cuda:
+            return self
+        flat = torch.cat([p.reshape(-1) for p in parts]).cpu()
+        out, o = {}, 0
+        for n, p in zip(names, parts):
+            out[n] = flat[o:o + p.numel()].view(p.shape)
+            o += p.numel()
+        return Forecast(**out)
+
+    def numpy(self):
+        """dict of numpy arrays (absent fields None)."""
+        host = self.cpu()
+        return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
+                for f in fields(host)}
+
+
+def _scale_vector(scale, R: int, device) -> Optional[torch.Tensor]:
+    """What ``_scale_forecast`` accepts (something with ``.values``, or array-like) -> (R,) fp64."""
+    if scale is None:
+        return None
+    if isinstance(scale, torch.Tensor):
+        s = scale.detach().to(device=device, dtype=torch.float64).reshape(-1)
+    else:
+        s = torch.from_numpy(np.asarray(scale.values if hasattr(scale, "values") else scale,
+                                        dtype=np.float64).reshape(-1)).to(device)
+    if s.numel() != R:
+        raise ValueError(f"scale has {s.numel()} entries for {R} regions")
+    return s.contiguous()
+
+
+def _ndtr(x: torch.Tensor) -> torch.Tensor:
+    return torch.special.ndtr(x)
+
+
+def _summary_torch(yhat, S, B, y_true, scale, q) -> Forecast:
+    T, N, R = yhat.shape
+    v = yhat.detach().to(torch.float64).reshape(T, S, B, R)
+    if scale is not None:
+        v = v * scale
+    mean = v.mean(1)
+    std = ((v - mean.unsqueeze(1)) ** 2).mean(1).sqrt()
+    out = Forecast(mean.permute(1, 0, 2).contiguous(), std.permute(1, 0, 2).contiguous())
+    if q is not None and q.numel() > 0:
+        out.quantiles = torch.quantile(v, q, dim=1).permute(0, 2, 1, 3).contiguous()     # (Q, T, B, R) -> (Q, B, T, R)
+    if y_true is not None:
+        y = y_true.detach().to(torch.float64).permute(1, 0, 2)                           # (T, B, R)
+        if scale is not None:
+            y = y * scale
+        z = (y - mean) / std
+        nll = 0.5 * z * z + std.log() + 0.5 * math.log(2 * math.pi)
+        mass = _ndtr((y + 0.6 - mean) / std) - _ndtr((y - 0.5 - mean) / std)
+        mass = torch.where(mass == 0, torch.full_like(mass, MASS_FLOOR), mass)
+        out.nll = nll.mean((1, 2))
+        out.skill = mass.log().mean((1, 2)).exp()
+        out.mae = (y - mean).abs().mean((1, 2))
+    return out
+
+
+def _library() -> Optional["_native.NativeLib"]:
+    """Any loaded / loadable library (the summary kernels have no model)."""
+    import os
+    if os.path.exists(_native.PREBUILT_LIB):
+        return _native.prebuilt()
+    for path in _native.loaded_paths():
+        return _native._load(path)
+    return None
+
+
+def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Optional[torch.Tensor] = None,
+                     scale=None, quantiles: Optional[Sequence[float]] = None) -> Forecast:
+    """Summary of ``yhat`` (T, S*B, R) (sample n = s*B + b, as the solve emits it) over its S
+    samples: see ``Forecast``.  ``scale``: per-region multiplier of predictions and targets (the
+    data scaler); ``y_true`` (B, T, R); ``quantiles``: levels in [0, 1] (numpy.quantile, 'linear').
+    A HIP tensor runs ude_forecast_summary; a CPU tensor (or no library) the same definitions in
+    torch fp64."""
+    if yhat.dim() != 3 or yhat.shape[1] != n_samples * batch:
+        raise ValueError(f"ensemble_summary: y_hat {tuple(yhat.shape)} is not (T, {n_samples}*{batch}, R)")
+    T, N, R = (int(v) for v in yhat.shape)
+    S, B = int(n_samples), int(batch)
+    if y_true is not None and tuple(y_true.shape) != (B, T, R):
+        raise ValueError(f"ensemble_summary: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
+    dev = yhat.device
+    sc = _scale_vector(scale, R, dev)
+    q = None
+    if quantiles is not None and len(quantiles) > 0:
+        q = torch.as_tensor(np.asarray(quantiles, dtype=np.float64), device=dev)
+        if bool(((q < 0) | (q > 1)).any()):
+            raise ValueError("ensemble_summary: quantile levels must lie in [0, 1]")
+        if S > MAX_QUANTILE_SAMPLES and yhat.is_cuda:
+            raise ValueError(f"ensemble_summary: quantiles need n_samples <= {MAX_QUANTILE_SAMPLES}")
+    lib = _library() if yhat.is_cuda else None
+    if lib is None:
+        return _summary_torch(yhat, S, B, y_true, sc, q)
+    n_q = 0 if q is None else int(q.numel())
+    yh = yhat.detach().to(torch.float32).contiguous()
+    yt = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
+    with torch.cuda.device(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        mean = torch.empty((B, T, R), **f64)
+        std = torch.empty((B, T, R), **f64)
+        quant = torch.empty((n_q, B, T, R), **f64) if n_q else None
+        scores = torch.empty((3, T), **f64) if yt is not None else None
+        ws = torch.empty(max(lib.forecast_summary_workspace(T, S, B, R, n_q) // 8, 1), **f64) if yt is not None else None
+        p = _fused._ptr
+        if _fused.EVENTS is not None:
+            e0 = _fused._ev(dev); e0.record()
+        lib.forecast_summary(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, p(ws), mean.data_ptr(),
+                             std.data_ptr(), p(quant), p(scores), _fused._stream(dev))
+        if _fused.EVENTS is not None:
+            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("forecast_summary", e0, e1))
+    out = Forecast(mean, std, quant)
+    if scores is not None:
+        out.nll, out.skill, out.mae = scores[0], scores[1].exp(), scores[2]
+    return out
+
+
+GRID_SNAP_ULPS = 8
+
+
+def _forecast_plan(ode, y0, t, step_size):
+    """The launch plan of the forecast solve.  The decoder epilogue needs every output time on the
+    grid.  torchdiffeq builds the grid of a ``step_size`` solve as ``t[0] + k * step`` in t's dtype; on
+    the forecast's daily grid ``arange(T) / 7`` with ``step = t[1] - t[0]`` (lib/utils.py:21 through
+    lib/VAE.py:137) that is ``k * fl(1/7)`` against ``t[k] = fl(k / 7)``: the same points up to a
+    rounding, which makes about half of the outputs "interpolations" with slope 1 - O(1e-7).  When the
+    two grids have the same length and agree to GRID_SNAP_ULPS roundings of the largest time, the
+    solve steps on ``t`` itself (torchdiffeq's grid without a step size): every output is then a grid
+    hit.  Against the interpolating schedule that moves an output by at most (1 - slope) = O(1e-6) of
+    one step's change, and each step size by a rounding of t."""
+    from . import solvers
+    from .schedule import fixed_grid
+    plan = solvers.plan_for(ode, y0, t, step_size)
+    if plan.out_k is not None or step_size is None:
+        return plan
+    th = t.detach().cpu()
+    grid = fixed_grid(th, step_size)
+    tol = GRID_SNAP_ULPS * torch.finfo(th.dtype).eps * float(th.abs().max())
+    if len(grid) == len(th) and float((grid - th).abs().max()) <= tol:
+        return solvers.plan_for(ode, y0, t, None)
+    return plan
+
+
+def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear) -> Optional[torch.Tensor]:
+    """y_hat (T, N, R) = Decoder(odeint(ode, y0, t)[..., :3]) of the inference solve
+    (ude_rk4_forecast_dec: no autograd, no latent, no checkpoint), or None when the decoder epilogue
+    does not apply (``decoder_head.eligible``) or an output time is not a grid point.  Records the
+    solve's side statistics on ``ode`` as every fused solve does (``posterior()``, the tracker)."""
+    if not decoder_head.eligible(ode, y0, linear):
+        return None
+    with torch.no_grad(), torch.cuda.device(y0.device):
+        plan = _forecast_plan(ode, y0, t, step_size)
+        if plan.out_k is None:
+            return None
+        dev = y0.device
+        stream = _fused._stream(dev)
+        sz = plan.sizes
+        y0 = y0.detach().contiguous()
+        if ode.uncertainty == "bayes":
+            mus, sds = ode.ude_mean_std()
+            eps = ode.take_eps(4 * plan.prob.n_steps, sum(int(p.numel()) for p in mus), dev).contiguous()
+            mus = [p.detach().contiguous() for p in mus]
+            sds = [p.detach().contiguous() for p in sds]
+            pack = torch.empty(max(sz.pack_bytes // 4, 1), dtype=torch.float32, device=dev)
+            plan.lib.pack_bayes(plan.desc, plan.prob, [w.data_ptr() for w in mus[0::2]],
+                                [b.data_ptr() for b in mus[1::2]], [w.data_ptr() for w in sds[0::2]],
+                                [b.data_ptr() for b in sds[1::2]], eps.data_ptr(), pack.data_ptr(), stream)
+        else:
+            params = []
+            for lin in ode.ude_linears():
+                params += [lin.weight, lin.bias]
+            pack = _fused.packed_weights(plan, params, dev)
+        Wd, bd = linear.weight.detach().contiguous(), linear.bias.detach().contiguous()
+        dec_pack = torch.empty(sz.dec_pack_bytes // 4, dtype=torch.float32, device=dev)
+        plan.lib.pack_decoder(plan.desc, Wd.data_ptr(), bd.data_ptr(), dec_pack.data_ptr(), stream)
+        N, R, L = y0.shape
+        yhat = torch.empty((plan.n_times, N, R), dtype=torch.float32, device=dev)
+        stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
+        stats, sums, st = _fused._stats_out(plan, dev)
+        if _fused.EVENTS is not None:
+            e0 = _fused._ev(dev); e0.record()
+        plan.lib.forecast_dec(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                              dec_pack.data_ptr(), yhat.data_ptr(), stats_slab.data_ptr(),
+                              _fused._ctl(plan, dev).data_ptr(), st, stream)
+        if _fused.EVENTS is not None:
+            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("forecast_dec", e0, e1))
+        ode._record_fused(stats, plan.n_eval, sums=sums)
+    return yhat

@@ -357,6 +357,32 @@ int ude_dopri_ratio(const float* err, const float* y0, const float* y1, double a
                     const int64_t* n, int32_t n_pieces, const double* extra, int32_t n_extra, double dt,
                     const unsigned char* flag, double* status, ude_stream_t stream);
 
+/* ---- the forecast (lib/utils.py:20-56 test, lib/VAE.py evaluate / validate) ---------------------
+ * ude_rk4_forecast_dec: the forward-only solve with the decoder epilogue.  Writes y_hat (T, N, R) =
+ * Decoder(latent[..., :3]) at every output time and the side statistics; no latent, no checkpoint, no
+ * stored activations, no final-state block and no latent_init_loss.  Preconditions of
+ * ude_rk4_forward_dec_ex (every output time a grid point, n_steps >= 1; UDE_E_INVALID otherwise);
+ * pack / dec_pack / sched / stats_slab / ctl / stats as there (ctl nullable: separate finalize launch).
+ * Bayesian kinds take the pack of ude_pack_weights_bayes.  y_hat equals ude_rk4_forward_dec's bit for
+ * bit.  Replaces model(x, t, n_samples, training=False)'s odeint + Decoder (lib/utils.py:21). */
+int ude_rk4_forecast_dec(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,
+                         const float* y0, const float* dec_pack, float* yhat, double* stats_slab, uint32_t* ctl,
+                         const UdeSideStats* stats, ude_stream_t stream);
+
+/* Ensemble summary of y_hat (T, S*B, R) (sample n = s*B + b; no model): for every group (t, b, r) the S
+ * values v_s = (double)y_hat[t, s*B+b, r] * scale[r] give mean, population std (ddof 0, two passes) and
+ * quant[k] = numpy.quantile(v, q[k]) ('linear'; S <= 1024 when n_q > 0, NaN inputs undefined); with
+ * targets y = (double)y_true[b, t, r] * scale[r], scores (3, T) = per time index the mean over its B*R
+ * groups of [-log N(y; mean, std), log(Phi((y+0.6-mean)/std) - Phi((y-0.5-mean)/std)) with an exactly
+ * zero mass replaced by 4.5399929762484854e-05, |y - mean|] = lib/Metrics.py nll / mb_log / mae (skill =
+ * exp of the second).  -1 targets are not masked (as lib/utils.py).  fp64 after the load; fixed-order
+ * sums, no atomics.  ws: ude_forecast_summary_workspace() bytes (only read with y_true).  Replaces the
+ * host copy + NumPy / SciPy of lib/utils.py:22-26 and :53-54. */
+int ude_forecast_summary_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int64_t* ws_bytes);
+int ude_forecast_summary(int32_t T, int32_t S, int32_t B, int32_t R, const float* yhat, const double* scale,
+                         const float* y_true, const double* q, int32_t n_q, void* ws, double* mean, double* std,
+                         double* quant, double* scores, ude_stream_t stream);
+
 /* Library build tag (for logs / tests). */
 const char* ude_build_info(void);
 

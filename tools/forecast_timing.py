@@ -1,0 +1,124 @@
+"""Time the forecast of the reference's test shape on the device: the host-scored path against the
+fused forecast.
+
+State model (R = 49, L = 8, FaFp [64, 64, 32] / [64, 64]), S = 128 samples of B = 64 windows
+(N = 8192 trajectories), t = arange(57) / 7 (run_ode.py's utils.test call).  After 5 warm-ups, 10
+runs each, wall clock between device synchronisations:
+
+  (a) host: model(x, t, 128, training=False) -> host copy -> NumPy mean / std -> Metrics.nll / skill
+      at the four horizons (lib/utils.py:21-26, :53-54);
+  (b) fused: model.forecast(x, t, 128, y_true, scaler).cpu().
+
+Per path: min / median / max of the wall clock, the span between a device event recorded before the
+call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
+(ude_amd.fused.EVENTS).  Prints one JSON line.
+
+    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128]
+"""
+import argparse
+import importlib
+import json
+import os
+import statistics
+import subprocess
+import sys
+import time
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+importlib.import_module("forecasting-influenza-using-universal-differential-equations_amd")
+
+import lib.Metrics as Metrics  # noqa: E402
+import lib.VAE as vae_mod  # noqa: E402
+import lib.models as models  # noqa: E402
+from ude_amd import fused  # noqa: E402
+
+
+def stats(xs):
+    return {"min": min(xs), "median": statistics.median(xs), "max": max(xs)}
+
+
+def timed(fn, runs, warmup):
+    for _ in range(warmup):
+        fn()
+    wall, span, kern = [], [], []
+    for _ in range(runs):
+        fused.EVENTS = []
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        e0.record()
+        fn(e1)
+        torch.cuda.synchronize()
+        wall.append((time.perf_counter() - t0) * 1e3)
+        span.append(e0.elapsed_time(e1))
+        per = {}
+        for kind, a, b in fused.EVENTS:
+            per[kind] = per.get(kind, 0.0) + a.elapsed_time(b)
+        kern.append(per)
+        fused.EVENTS = None
+    native = {kind: stats([k[kind] for k in kern]) for kind in kern[0]}
+    return {"wall_ms": stats(wall), "device_span_ms": stats(span), "native_calls_ms": native}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--runs", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--batch", type=int, default=64)
+    ap.add_argument("--samples", type=int, default=128)
+    a = ap.parse_args()
+    R, B, S, window = 49, a.batch, a.samples, 8
+    torch.manual_seed(0)
+    model = vae_mod.VAE(models.Encoder_Back_GRU, models.FaFp, models.Decoder, 8, 8, R,
+                        ode_params={"net_sizes": [64, 64, 32], "aug_net_sizes": [64, 64]},
+                        enc_params={"q_sizes": [32, 16], "ff_sizes": [16, 16], "SIR_scaler": [0.1, 0.05, 1.0]},
+                        uncertainty=True).to("cuda")
+    gen = torch.Generator().manual_seed(1)
+    x = torch.rand(B, window, R * 9, generator=gen).cuda()
+    t = torch.arange(57, dtype=torch.float32) / 7
+    scaler = np.linspace(2.0, 9.0, R)
+    y_test = (torch.rand(B, 57, R, generator=gen) * 0.5).cuda()
+    horizons = [window + 6, window + 13, window + 20, window + 27]
+
+    def host(e1=None):
+        y_pred = model(x, t, n_samples=S, training=False)
+        y_pr = y_pred.detach().cpu().numpy() * scaler[None, None, None, :]
+        if e1 is not None:
+            e1.record()
+        y_te = y_test.detach().cpu().numpy() * scaler[None, None, :]
+        mu, sd = y_pr.mean(1), y_pr.std(1)
+        return [(Metrics.nll(y_te[:, g, :], mu[:, g, :], sd[:, g, :]),
+                 Metrics.skill(y_te[:, g, :], mu[:, g, :], sd[:, g, :])) for g in horizons]
+
+    def fusedf(e1=None):
+        fc = model.forecast(x, t, n_samples=S, y_true=y_test, scaler=scaler).cpu()
+        if e1 is not None:
+            e1.record()
+        return [(float(fc.nll[g]), float(fc.skill[g])) for g in horizons]
+
+    torch.manual_seed(7)
+    ra = host()
+    torch.manual_seed(7)                                   # the same draw: the two paths' scores agree
+    rb = fusedf()
+    agree = max(abs(p - q) / max(abs(q), 1e-30) for u, v in zip(rb, ra) for p, q in zip(u, v))
+    res_a = timed(host, a.runs, a.warmup)
+    res_b = timed(fusedf, a.runs, a.warmup)
+    try:
+        commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True,
+                                text=True).stdout.strip() or None
+    except OSError:
+        commit = None
+    out = {"tool": "forecast_timing", "commit": commit, "device": torch.cuda.get_device_name(0),
+           "shape": {"R": R, "L": 8, "S": S, "B": B, "N": S * B, "T": 57},
+           "latent_path_used_by_forecast": model.latent is not None,
+           "scores_rel_diff_fused_vs_host": agree, "host": res_a, "fused": res_b,
+           "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
