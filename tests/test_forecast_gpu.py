@@ -26,22 +26,30 @@ def _summary(yhat, S, B, scale, y, q):
                             scale=scale, quantiles=q)
 
 
-@pytest.mark.parametrize("shape,targets,ties", [
-    ((3, 5, 4, 1), True, False),          # odd S, 12 groups: fewer than a wave
-    ((2, 128, 3, 49), True, False),       # B * R = 147: no multiple of any tile width
-    ((2, 64, 7, 10), True, True),         # repeated values inside every group
-    ((1, 1024, 2, 3), True, False),       # the largest S with quantiles
-    ((2, 1, 5, 2), False, False),         # S = 1: std 0
-])
-def test_summary_kernel_matches_numpy(pkg, shape, targets, ties):
+@pytest.mark.parametrize("shape,targets,ties,q,scaled", [
+    ((3, 5, 4, 1), True, False, LEVELS, True),          # odd S, 12 groups: fewer than a wave
+    ((2, 128, 3, 49), True, False, LEVELS, True),       # B * R = 147: no multiple of any tile width
+    ((2, 64, 7, 10), True, True, LEVELS, True),         # repeated values inside every group
+    ((1, 1024, 2, 3), True, False, LEVELS, True),       # the largest S with quantiles
+    ((2, 1, 5, 2), False, False, LEVELS, True),         # S = 1: std 0
+    ((1, 4100, 1, 3), True, False, None, True),         # S above the tile: rows == 0, y_hat read twice
+    ((1, 3000, 2, 3), True, False, None, True),         # a tile of 3000 rows (no power of two), G = 1
+    ((2, 2, 90, 49), True, False, LEVELS, True),        # nbx = 69 > 64: the scores kernel's strided loop
+    ((2, 9, 3, 10), True, False, LEVELS, False),        # no scale vector
+], ids=["shape0-True-False", "shape1-True-False", "shape2-True-True", "shape3-True-False", "shape4-False-False",
+        "untiled_S4100", "tile_3000_rows_G1", "nbx69", "no_scale"])
+def test_summary_kernel_matches_numpy(pkg, shape, targets, ties, q, scaled):
     T, S, B, R = shape
     yhat, scale, y = synth(T, S, B, R, seed=100 + S, targets=targets, ties=ties)
-    ref = numpy_summary(yhat, S, B, scale, y, LEVELS)
+    if not scaled:
+        scale = None
+    ref = numpy_summary(yhat, S, B, scale, y, q)
     if targets:
         assert np.exp(ref["mb_log"]).min() >= 1e-6        # the group masses are larger still
-    fc = _summary(yhat, S, B, scale, y, LEVELS)
+    fc = _summary(yhat, S, B, scale, y, q)
     torch.cuda.synchronize()
-    keys = ("mean", "std", "quantiles") + (("nll", "mae") if targets else ())
+    assert (fc.quantiles is None) == (q is None)
+    keys = ("mean", "std") + (("quantiles",) if q is not None else ()) + (("nll", "mae") if targets else ())
     errs = {k: normwise_rel(getattr(fc, k), ref[k]) for k in keys}
     if targets:
         errs["mb_log"] = normwise_rel(fc.skill.log(), ref["mb_log"])
@@ -51,7 +59,7 @@ def test_summary_kernel_matches_numpy(pkg, shape, targets, ties):
         errs.pop("std")
     for k, e in errs.items():
         assert e <= (1e-8 if k == "mb_log" else 1e-10), (k, e)
-    again = _summary(yhat, S, B, scale, y, LEVELS)
+    again = _summary(yhat, S, B, scale, y, q)
     for k in ("mean", "std", "quantiles", "nll", "skill", "mae"):
         a, b = getattr(fc, k), getattr(again, k)
         assert (a is None and b is None) or torch.equal(a, b), k
