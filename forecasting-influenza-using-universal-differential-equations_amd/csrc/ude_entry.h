@@ -1,5 +1,14 @@
 // Host-side launch logic for one compiled model configuration (Ops<M>) and
 // the type-erased registry entry the C-ABI (ude_rk4.hip) dispatches on.
+//
+// Where things are added:
+//  - a new ude_fwd_kernel variant: one row of Ops<M>::fwd_variant, and nowhere else.  The rows are the
+//    only place the kernel's template-id is written; the LDS attribute setup (ensure_attrs), the
+//    occupancy query (grid_fwd) and the launch (launch_forward) all reach the kernel through them, and
+//    a row is also what makes the device pass emit that kernel (ude_cfg.hip).
+//  - a new forward entry (another set of outputs): a thin function like forward / forward_dec /
+//    forecast_dec that validates, fills the KArgs fields only it has, and calls launch_forward.
+//  - a persistent kernel's grid: occupancy_grid.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -34,6 +43,20 @@ bool matches(const UdeModelDesc* d) {
 
 #define HIPCHK(x) do { if ((x) != hipSuccess) return UDE_E_HIP; } while (0)
 
+// The grid of a persistent kernel over `work` items: one workgroup per resident slot of the device
+// (CUs x the kernel's occupancy at this block size and dynamic LDS), at most one per item, at least one.
+inline int occupancy_grid(const void* kernel, int threads, size_t lds, int device, long work, int* grid,
+                          int* cus_out = nullptr) {
+  int cus = 0, occ = 0;
+  HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
+  HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, kernel, threads, lds));
+  const long mx = (long)cus * (occ < 1 ? 1 : occ);
+  const long g = work < mx ? work : mx;
+  *grid = g < 1 ? 1 : (int)g;
+  if (cus_out) *cus_out = cus;
+  return UDE_OK;
+}
+
 template <class M> struct is_recompute { static constexpr bool value = false; };
 template <class B> struct is_recompute<Recompute<B>> { static constexpr bool value = true; };
 
@@ -45,27 +68,57 @@ struct Ops {
     return (int64_t)p->n_steps * 4 + (int64_t)(p->n_steps + 1) * 4 + (int64_t)p->n_out * 12;
   }
   static_assert(!M::HOIST || DY0_STATIC_LDS <= 160 * 1024, "dy0 static time sums do not fit the 160 KiB LDS");
+
+  // ---- the forward kernel's variants ---------------------------------------------------------------
+  // One row per ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES> this model has:
+  //   train: stores the training checkpoint;  dec: the decoder epilogue (y_hat, no latent);
+  //   split: the 8-wave kernel (Model::SPLIT_FWD);  res: resident weights, one workgroup per CU
+  //   (Model::FWD_RES).
+  // fwd_variant calls f(kernel, threads, dynamic LDS bytes) for the row of the given facts and returns
+  // f's result, or NO_VARIANT when the model has no such kernel.  Inference with the decoder epilogue
+  // (the forecast) stores nothing, so the Recompute view has none.
+  static constexpr int NO_VARIANT = 1;
+  template <bool TRAIN, bool DEC, bool SPLIT, bool RES, class F>
+  static int fwd_row(F&& f) {
+    return f((const void*)&ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES>, SPLIT ? 2 * NTHREADS : NTHREADS,
+             DEC ? M::LDS_F_DEC : M::LDS_F);
+  }
+  template <class F>
+  static int fwd_variant(bool train, bool dec, bool split, bool res, F&& f) {
+    const auto is = [=](bool t, bool d, bool s, bool r) { return train == t && dec == d && split == s && res == r; };
+    if (is(1, 0, 0, 0)) return fwd_row<true, false, false, false>(f);
+    if (is(0, 0, 0, 0)) return fwd_row<false, false, false, false>(f);
+    if (is(1, 1, 0, 0)) return fwd_row<true, true, false, false>(f);
+    if constexpr (M::SPLIT_FWD) {
+      if (is(1, 0, 1, 0)) return fwd_row<true, false, true, false>(f);
+      if (is(1, 1, 1, 0)) return fwd_row<true, true, true, false>(f);
+    }
+    if constexpr (M::FWD_RES) {
+      if (is(1, 0, 0, 1)) return fwd_row<true, false, false, true>(f);
+      if (is(0, 0, 0, 1)) return fwd_row<false, false, false, true>(f);
+      if (is(1, 1, 0, 1)) return fwd_row<true, true, false, true>(f);
+    }
+    if constexpr (!is_recompute<M>::value) {
+      if (is(0, 1, 0, 0)) return fwd_row<false, true, false, false>(f);
+      if constexpr (M::FWD_RES) {
+        if (is(0, 1, 0, 1)) return fwd_row<false, true, false, true>(f);
+      }
+    }
+    return NO_VARIANT;
+  }
+
   static int ensure_attrs() {
     static bool done = false;
     if (done) return UDE_OK;
-    // record + (when it fits) the schedule: up to the full 160 KiB
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, M::SPLIT_FWD>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, false, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, M::SPLIT_FWD, true>,
-                               hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    // the inference decoder forward (forecast_dec; it stores nothing, so the Recompute view has none)
-    if constexpr (!is_recompute<M>::value) {
-      HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      if constexpr (M::FWD_RES)
-        HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false, false, true, true>,
-                                   hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+    // record + (when it fits) the schedule: up to the full 160 KiB, for every forward variant there is
+    for (int v = 0; v < 16; ++v) {
+      const int rc = fwd_variant(v & 1, v & 2, v & 4, v & 8, [](const void* k, int, int) -> int {
+        HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
+        return UDE_OK;
+      });
+      if (rc != UDE_OK && rc != NO_VARIANT) return rc;
     }
+    HIPCHK(hipFuncSetAttribute((const void*)&ude_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)&ude_dec_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                DecBwdDims<M>::LDS));
     // the static-feature dy0 kernel stages one tile's (16, R, L) time sums of d latent in LDS
@@ -77,34 +130,25 @@ struct Ops {
                                  Gst<M>::LDS));
     HIPCHK(hipFuncSetAttribute((const void*)&ude_bwd_tail_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                Tail<M>::LDS));
-    if constexpr (M::FWD_RES) {
-      HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, false, false, false, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-      HIPCHK(hipFuncSetAttribute((const void*)&ude_fwd_kernel<M, true, false, true, true>,
-                                 hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
-    }
     done = true;
     return UDE_OK;
   }
 
-  static int grids(int device, int n_tiles, int* gf, int* gb) {
+  static int n_tiles_of(const UdeProblem* p) { return (p->n_traj + TT - 1) / TT; }
+
+  // forward grid (the plain training kernel's occupancy; stats_slab / reg_slab are sized by it) and
+  // backward grid; cus: the device's CU count, for the callers that need it as well
+  static int grid_fwd(int device, int n_tiles, int* gf, int* cus = nullptr) {
     int rc = ensure_attrs();
     if (rc) return rc;
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    int of = 0, ob = 0;
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, (const void*)&ude_fwd_kernel<M, true>, NTHREADS, M::LDS_F));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, (const void*)&ude_bwd_kernel<M>, M::BWD_THREADS, M::LDS_B));
-    if (of < 1) of = 1;
-    if (ob < 1) ob = 1;
-    const long mf = (long)cus * of, mb = (long)cus * ob;
-    *gf = (int)(n_tiles < mf ? n_tiles : mf);
-    *gb = (int)(n_tiles < mb ? n_tiles : mb);
-    if (*gf < 1) *gf = 1;
-    if (*gb < 1) *gb = 1;
-    return UDE_OK;
+    return fwd_variant(true, false, false, false, [&](const void* k, int threads, int lds) {
+      return occupancy_grid(k, threads, lds, device, n_tiles, gf, cus);
+    });
+  }
+  static int grid_bwd(int device, int n_tiles, int* gb, int* cus = nullptr) {
+    int rc = ensure_attrs();
+    if (rc) return rc;
+    return occupancy_grid((const void*)&ude_bwd_kernel<M>, M::BWD_THREADS, M::LDS_B, device, n_tiles, gb, cus);
   }
 
   // grad-slab workspace tail (HOIST): G0 [tile][K0][16] + split-K partials [chunks][K0][S16]
@@ -112,6 +156,11 @@ struct Ops {
     if (!M::HOIST) return 0;
     const int64_t legacy = (int64_t)M::STATIC_CHUNKS * M::K0 * M::S16, tail = Tail<M>::part_floats();
     return (int64_t)n_tiles * M::K0 * TT + (legacy > tail ? legacy : tail);
+  }
+  // ... and where the two parts lie in a slab of gb workgroup slabs (backward, EvalOps::eval_vjp)
+  static void static_ws(float* slab, int gb, int n_tiles, float** g0buf, float** part) {
+    *g0buf = slab + (size_t)gb * M::SLAB_STRIDE;
+    *part = *g0buf + (size_t)n_tiles * M::K0 * TT;
   }
   // control words of the *_ex calls: [0] the forward's arrival counter, [1 + st] the tail's static
   // column tiles (include/ude_rk4.h)
@@ -174,9 +223,11 @@ struct Ops {
     }
     if (p->n_traj < 1 || p->n_steps < 0 || p->n_out < 0) return UDE_E_INVALID;
     if (M::BAYES && 4 * (int64_t)p->n_steps > 65535) return UDE_E_INVALID;   // grid.y / grid.z of the packers
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
-    int gf = 1, gb = 1;
-    int rc = grids(device, n_tiles, &gf, &gb);
+    const int n_tiles = n_tiles_of(p);
+    int gf = 1, gb = 1, cus = 0;
+    int rc = grid_fwd(device, n_tiles, &gf, &cus);
+    if (rc) return rc;
+    rc = grid_bwd(device, n_tiles, &gb);
     if (rc) return rc;
     const int64_t ne = n_evals(p) > 0 ? n_evals(p) : 1;
     // BAYES: [eval][PACK_TOTAL] weight samples, then [eval][SLAB_TOTAL] eps in slab order
@@ -189,8 +240,6 @@ struct Ops {
     o->stats_slab_bytes = (int64_t)gf * 5 * 8;
     o->grad_slab_bytes = (int64_t)gb * M::SLAB_STRIDE * 4 + static_ws_floats(n_tiles) * 4;
     if constexpr (M::GST) {
-      int cus = 0;
-      HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
       o->grad_slab_bytes = (gst_rows_floats(n_tiles, p->n_steps) +
                             n_evals(p) * gst_ks(cus, n_evals(p), n_tiles) * (int64_t)M::SLAB_TOTAL) * 4;
     }
@@ -214,15 +263,7 @@ struct Ops {
   static int dec_grid(int device, int n_tiles, int* g) {
     int rc = ensure_attrs();
     if (rc) return rc;
-    int cus = 0, occ = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)&ude_dec_bwd_kernel<M>, NTHREADS,
-                                                        DecBwdDims<M>::LDS));
-    if (occ < 1) occ = 1;
-    const long mx = (long)cus * occ;
-    *g = (int)(n_tiles < mx ? n_tiles : mx);
-    if (*g < 1) *g = 1;
-    return UDE_OK;
+    return occupancy_grid((const void*)&ude_dec_bwd_kernel<M>, NTHREADS, DecBwdDims<M>::LDS, device, n_tiles, g);
   }
 
   static int dec_pack(const float* W, const float* b, float* out, hipStream_t s) {
@@ -247,42 +288,12 @@ struct Ops {
         !stats_ok(st))
       return UDE_E_INVALID;
     if (p->n_steps < 1) return UDE_E_INVALID;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
-    int gf = 1, gb = 1;
-    int rc = grids(dev, n_tiles, &gf, &gb);
-    if (rc) return rc;
     KArgs a;
     memset(&a, 0, sizeof(a));
-    a.pack = pack; a.y0 = y0; a.sched = (const unsigned char*)sched;
-    a.ckpt = ckpt; a.stats_slab = stats_slab;
-    a.dec_pack = dec_pack; a.yhat = yhat; a.reg_slab = reg_slab;
-    a.ckpt_final = ckpt + ckpt_final_off<M>(n_tiles, p->n_steps);
-    a.n_traj = p->n_traj; a.n_steps = p->n_steps; a.n_out = p->n_out; a.n_tiles = n_tiles;
-    a.fa_w = p->fa_w;
-    const double n_eval = 4.0 * (double)p->n_steps * (double)p->n_traj * (double)M::R;
-    set_stats_out(a, st, ctl, n_eval);
-    a.o_reg = reg_out;
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    // the resident-weight forward runs one workgroup per CU (min(n_tiles, cus) <= gf slabs)
-    const bool res = !(M::SPLIT_FWD && n_tiles <= cus) && fwd_res(n_tiles, cus);
-    if (res) gf = n_tiles < cus ? n_tiles : cus;
-    if (M::SPLIT_FWD && n_tiles <= cus)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, true, M::SPLIT_FWD, true>), dim3(gf), dim3(2 * NTHREADS), M::LDS_F_DEC, s, a);
-    else if (res)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, true, false, true, M::FWD_RES>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
-    else hipLaunchKernelGGL((ude_fwd_kernel<M, true, false, true>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
-    HIPCHK(hipGetLastError());
-    if (!ctl) {
-      hipLaunchKernelGGL(ude_stats_finalize_kernel<0>, dim3(1), dim3(320), 0, s, stats_slab, gf, n_eval, a.o_mean,
-                         a.o_std, a.o_norm);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL(ude_sum_finalize_kernel<0>, dim3(1), dim3(64), 0, s, (const double*)reg_slab, gf, reg_out);
-      HIPCHK(hipGetLastError());
-    }
-    return UDE_OK;
+    a.ckpt = ckpt;
+    a.ckpt_final = ckpt + ckpt_final_off<M>(n_tiles_of(p), p->n_steps);
+    a.dec_pack = dec_pack; a.yhat = yhat; a.reg_slab = reg_slab; a.o_reg = reg_out;
+    return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
   }
 
   // Inference forward with the decoder epilogue (the forecast): y_hat (T, N, R) and the side statistics;
@@ -298,40 +309,10 @@ struct Ops {
     if (!pack || !sched || !y0 || !dec_pack || !yhat || !stats_slab || !stats_ok(st) || (!reg_slab) != (!reg_out))
       return UDE_E_INVALID;
     if (p->n_steps < 1) return UDE_E_INVALID;
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
-    int gf = 1, gb = 1;
-    int rc = grids(dev, n_tiles, &gf, &gb);
-    if (rc) return rc;
     KArgs a;
     memset(&a, 0, sizeof(a));
-    a.pack = pack; a.y0 = y0; a.sched = (const unsigned char*)sched;
-    a.stats_slab = stats_slab;
-    a.dec_pack = dec_pack; a.yhat = yhat; a.reg_slab = reg_slab;
-    a.n_traj = p->n_traj; a.n_steps = p->n_steps; a.n_out = p->n_out; a.n_tiles = n_tiles;
-    a.fa_w = p->fa_w;
-    const double n_eval = 4.0 * (double)p->n_steps * (double)p->n_traj * (double)M::R;
-    set_stats_out(a, st, ctl, n_eval);
-    a.o_reg = reg_out;
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const bool res = fwd_res(n_tiles, cus);
-    if (res) gf = n_tiles < cus ? n_tiles : cus;
-    if (res)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, false, false, true, M::FWD_RES>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
-    else hipLaunchKernelGGL((ude_fwd_kernel<M, false, false, true>), dim3(gf), dim3(NTHREADS), M::LDS_F_DEC, s, a);
-    HIPCHK(hipGetLastError());
-    if (!ctl) {
-      hipLaunchKernelGGL(ude_stats_finalize_kernel<0>, dim3(1), dim3(320), 0, s, stats_slab, gf, n_eval, a.o_mean,
-                         a.o_std, a.o_norm);
-      HIPCHK(hipGetLastError());
-      if (reg_slab) {
-        hipLaunchKernelGGL(ude_sum_finalize_kernel<0>, dim3(1), dim3(64), 0, s, (const double*)reg_slab, gf, reg_out);
-        HIPCHK(hipGetLastError());
-      }
-    }
-    return UDE_OK;
+    a.dec_pack = dec_pack; a.yhat = yhat; a.reg_slab = reg_slab; a.o_reg = reg_out;
+    return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
     }
   }
 
@@ -472,40 +453,55 @@ struct Ops {
     if (!pack || !sched || !y0 || !latent || !stats_slab || !stats_ok(st)) return UDE_E_INVALID;
     if (M::L == 8 && (reinterpret_cast<uintptr_t>(latent) & 15))
       return UDE_E_INVALID;                          // the row-mapped tile start writes 16-B latent rows
-    int dev = 0;
-    HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
-    int gf = 1, gb = 1;
-    int rc = grids(dev, n_tiles, &gf, &gb);
-    if (rc) return rc;
     KArgs a;
     memset(&a, 0, sizeof(a));
+    a.latent = latent; a.ckpt = ckpt;
+#ifdef UDE_PROFILE
+    a.prof = g_prof_buffer ? g_prof_buffer + (size_t)PROF_FWD_SLOT * NPROF : nullptr;   // behind the backward's
+#endif
+    return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
+  }
+
+  // The one forward launch behind forward / forward_dec / forecast_dec.  `a` arrives zeroed except for
+  // what only its entry has (outputs, checkpoint, decoder pack); a.ckpt says whether the solve stores
+  // the training checkpoint, a.yhat whether it runs the decoder epilogue.  Kernel selection:
+  //   split    iff it stores a checkpoint, the model has the 8-wave kernel and every tile has a CU of
+  //            its own (so an inference solve, the forecast included, never splits);
+  //   resident else iff fwd_res(): one workgroup per CU, gf = min(n_tiles, cus) (<= the slabs' size);
+  //   plain    else.
+  // ctl == null (the legacy entries): the statistics and latent_init_loss are finalized by separate launches.
+  static int launch_forward(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
+                            double* stats_slab, const UdeSideStats* st, unsigned* ctl, KArgs& a, hipStream_t s) {
+    int dev = 0;
+    HIPCHK(hipGetDevice(&dev));
+    const int n_tiles = n_tiles_of(p);
+    int gf = 1, cus = 0;
+    int rc = grid_fwd(dev, n_tiles, &gf, &cus);
+    if (rc) return rc;
     a.pack = pack; a.y0 = y0; a.sched = (const unsigned char*)sched;
-    a.latent = latent; a.ckpt = ckpt; a.stats_slab = stats_slab;
+    a.stats_slab = stats_slab;
     a.n_traj = p->n_traj; a.n_steps = p->n_steps; a.n_out = p->n_out; a.n_tiles = n_tiles;
     a.fa_w = p->fa_w;
     const double n_eval = 4.0 * (double)p->n_steps * (double)p->n_traj * (double)M::R;
     set_stats_out(a, st, ctl, n_eval);
-#ifdef UDE_PROFILE
-    a.prof = g_prof_buffer ? g_prof_buffer + (size_t)PROF_FWD_SLOT * NPROF : nullptr;   // behind the backward's
-#endif
-    int cus = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
-    const bool res = !(ckpt && M::SPLIT_FWD && n_tiles <= cus) && fwd_res(n_tiles, cus);
+    const bool train = a.ckpt != nullptr, dec = a.yhat != nullptr;
+    const bool split = train && M::SPLIT_FWD && n_tiles <= cus;
+    const bool res = !split && fwd_res(n_tiles, cus);
     if (res) gf = n_tiles < cus ? n_tiles : cus;
-    if (ckpt && M::SPLIT_FWD && n_tiles <= cus)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, true, M::SPLIT_FWD>), dim3(gf), dim3(2 * NTHREADS), M::LDS_F, s, a);
-    else if (res && ckpt)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, true, false, false, M::FWD_RES>), dim3(gf), dim3(NTHREADS), M::LDS_F, s, a);
-    else if (res)
-      hipLaunchKernelGGL((ude_fwd_kernel<M, false, false, false, M::FWD_RES>), dim3(gf), dim3(NTHREADS), M::LDS_F, s, a);
-    else if (ckpt) hipLaunchKernelGGL((ude_fwd_kernel<M, true>), dim3(gf), dim3(NTHREADS), M::LDS_F, s, a);
-    else hipLaunchKernelGGL((ude_fwd_kernel<M, false>), dim3(gf), dim3(NTHREADS), M::LDS_F, s, a);
-    HIPCHK(hipGetLastError());
+    rc = fwd_variant(train, dec, split, res, [&](const void* k, int threads, int lds) -> int {
+      void* args[] = {&a};
+      HIPCHK(hipLaunchKernel(k, dim3(gf), dim3(threads), args, lds, s));
+      return UDE_OK;
+    });
+    if (rc) return rc == NO_VARIANT ? UDE_E_UNSUPPORTED : rc;
     if (!ctl) {
       hipLaunchKernelGGL(ude_stats_finalize_kernel<0>, dim3(1), dim3(320), 0, s, stats_slab, gf, n_eval, a.o_mean,
                          a.o_std, a.o_norm);
       HIPCHK(hipGetLastError());
+      if (a.reg_slab) {
+        hipLaunchKernelGGL(ude_sum_finalize_kernel<0>, dim3(1), dim3(64), 0, s, (const double*)a.reg_slab, gf, a.o_reg);
+        HIPCHK(hipGetLastError());
+      }
     }
     return UDE_OK;
   }
@@ -524,9 +520,9 @@ struct Ops {
     if (p->n_steps > 0 && !ckpt) return UDE_E_INVALID;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
-    int gf = 1, gb = 1;
-    int rc = grids(dev, n_tiles, &gf, &gb);
+    const int n_tiles = n_tiles_of(p);
+    int gb = 1, cus = 0;
+    int rc = grid_bwd(dev, n_tiles, &gb, &cus);
     if (rc) return rc;
     KArgs a;
     memset(&a, 0, sizeof(a));
@@ -536,8 +532,8 @@ struct Ops {
     if (dst) { a.d_mean = dst->d_mean; a.d_std = dst->d_std; a.d_norm = dst->d_fa_norm; }
     a.dy0 = dy0; a.slab = slab;
     if (M::BAYES) a.eslab = pack + (size_t)n_evals(p) * M::PACK_TOTAL;
-    float* g0buf = slab + (size_t)gb * M::SLAB_STRIDE;
-    float* part = g0buf + (size_t)n_tiles * M::K0 * TT;
+    float *g0buf, *part;
+    static_ws(slab, gb, n_tiles, &g0buf, &part);
     a.g0buf = g0buf;
 #ifdef UDE_PROFILE
     a.prof = g_prof_buffer;
@@ -547,8 +543,6 @@ struct Ops {
     if constexpr (M::GST) {
       // the backward stores the layer-output gradient rows; ude_gst_dw_kernel forms every evaluation's
       // weight gradient from them and the stored rows, ude_gst_reduce_kernel sums / eps-weights them
-      int cus = 0;
-      HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev));
       const int64_t ne = n_evals(p);
       const int ks = gst_ks(cus, ne, n_tiles);
       a.gst = slab;
@@ -618,14 +612,7 @@ struct DopriOps {
       HIPCHK(hipFuncSetAttribute((const void*)&ude_dopri_kernel<M, dp::MODE_STEP>, hipFuncAttributeMaxDynamicSharedMemorySize, M::LDS_F));
       done = true;
     }
-    int cus = 0, occ = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)&ude_dopri_kernel<M, dp::MODE_STEP>, NTHREADS, M::LDS_F));
-    if (occ < 1) occ = 1;
-    const long mx = (long)cus * occ;
-    *grid = (int)(n_tiles < mx ? n_tiles : mx);
-    if (*grid < 1) *grid = 1;
-    return UDE_OK;
+    return occupancy_grid((const void*)&ude_dopri_kernel<M, dp::MODE_STEP>, NTHREADS, M::LDS_F, device, n_tiles, grid);
   }
 
   static Layout layout(int n_tiles, int grid) {
@@ -733,16 +720,8 @@ struct LossOps {
       HIPCHK(hipFuncSetAttribute((const void*)&ude_loss_kernel<D, M::L, true>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
       done = true;
     }
-    int cus = 0, occ = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    if (bwd)
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)&ude_loss_kernel<D, M::L, true>, LTHREADS, lds));
-    else
-      HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&occ, (const void*)&ude_loss_kernel<D, M::L, false>, LTHREADS, lds));
-    if (occ < 1) occ = 1;
-    const long mx = (long)cus * occ, groups = (long)T * B;
-    *g = (int)(groups < mx ? groups : mx);
-    return UDE_OK;
+    const void* k = bwd ? (const void*)&ude_loss_kernel<D, M::L, true> : (const void*)&ude_loss_kernel<D, M::L, false>;
+    return occupancy_grid(k, LTHREADS, lds, device, (long)T * B, g);
   }
   static Layout layout(int T, int B, int gf, int gb) {
     auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
@@ -828,15 +807,9 @@ struct EvalOps {
                                  Tail<M>::LDS));
       done = true;
     }
-    int cus = 0, of = 0, ob = 0;
-    HIPCHK(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, device));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&of, (const void*)&ude_eval_fwd_kernel<M>, NTHREADS, M::LDS_F));
-    HIPCHK(hipOccupancyMaxActiveBlocksPerMultiprocessor(&ob, (const void*)&ude_eval_vjp_kernel<M>, eval_vjp_threads<M>(),
-                                                           M::LDS_B));
-    const long mf = (long)cus * (of < 1 ? 1 : of), mb = (long)cus * (ob < 1 ? 1 : ob);
-    *gf = (int)(n_tiles < mf ? n_tiles : mf);
-    *gb = (int)(n_tiles < mb ? n_tiles : mb);
-    return UDE_OK;
+    int rc = occupancy_grid((const void*)&ude_eval_fwd_kernel<M>, NTHREADS, M::LDS_F, device, n_tiles, gf);
+    if (rc) return rc;
+    return occupancy_grid((const void*)&ude_eval_vjp_kernel<M>, eval_vjp_threads<M>(), M::LDS_B, device, n_tiles, gb);
     }
   }
   // workspace: dW slab [gb][SLAB_STRIDE], G0 + static partials (HOIST), the tail's ticket words
@@ -897,9 +870,8 @@ struct EvalOps {
     int gf = 1, gb = 1;
     int rc = grids(dev, n_tiles, &gf, &gb);
     if (rc) return rc;
-    float* slab = (float*)ws;
-    float* g0buf = slab + (size_t)gb * M::SLAB_STRIDE;
-    float* part = g0buf + (size_t)n_tiles * M::K0 * TT;
+    float *slab = (float*)ws, *g0buf, *part;
+    Ops<M>::static_ws(slab, gb, n_tiles, &g0buf, &part);
     EArgs a;
     memset(&a, 0, sizeof(a));
     a.pack = pack; a.x = x; a.cot_f = cot_f; a.cot_rates = cot_rates; a.cot_fa = cot_fa;

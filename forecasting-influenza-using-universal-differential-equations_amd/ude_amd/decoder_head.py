@@ -97,11 +97,8 @@ class _NllHead(torch.autograd.Function):
         ws = torch.empty(max(lib.nll_workspace(desc, T, S, B) // 4, 1), dtype=torch.float32, device=dev)
         out = torch.empty(1, dtype=torch.float32, device=dev)
         yhat, y = yhat.contiguous(), y.contiguous()
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
-        lib.nll_forward(desc, T, S, B, yhat.data_ptr(), y.data_ptr(), ws.data_ptr(), out.data_ptr(), stream)
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("nll_fwd", e0, e1))
+        with _fused._timed("nll_fwd"):
+            lib.nll_forward(desc, T, S, B, yhat.data_ptr(), y.data_ptr(), ws.data_ptr(), out.data_ptr(), stream)
         ctx.meta = (lib, desc, T, S, B)
         ctx.save_for_backward(yhat, y, ws)
         ctx.mark_non_differentiable(ws)
@@ -114,12 +111,9 @@ class _NllHead(torch.autograd.Function):
         dev = yhat.device
         grad = torch.zeros(1, dtype=torch.float32, device=dev) if g is None else g.reshape(1).float()
         dyhat = torch.empty_like(yhat)
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
-        lib.nll_backward(desc, T, S, B, yhat.data_ptr(), y.data_ptr(), grad.data_ptr(), ws.data_ptr(),
-                         dyhat.data_ptr(), _fused._stream(dev))
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("nll_bwd", e0, e1))
+        with _fused._timed("nll_bwd"):
+            lib.nll_backward(desc, T, S, B, yhat.data_ptr(), y.data_ptr(), grad.data_ptr(), ws.data_ptr(),
+                             dyhat.data_ptr(), _fused._stream(dev))
         return None, None, None, None, None, dyhat, None
 
 

@@ -155,12 +155,9 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
         scores = torch.empty((3, T), **f64) if yt is not None else None
         ws = torch.empty(max(lib.forecast_summary_workspace(T, S, B, R, n_q) // 8, 1), **f64) if yt is not None else None
         p = _fused._ptr
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
-        lib.forecast_summary(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, p(ws), mean.data_ptr(),
-                             std.data_ptr(), p(quant), p(scores), _fused._stream(dev))
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("forecast_summary", e0, e1))
+        with _fused._timed("forecast_summary"):
+            lib.forecast_summary(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, p(ws), mean.data_ptr(),
+                                 std.data_ptr(), p(quant), p(scores), _fused._stream(dev))
     out = Forecast(mean, std, quant)
     if scores is not None:
         out.nll, out.skill, out.mae = scores[0], scores[1].exp(), scores[2]
@@ -210,13 +207,8 @@ def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
         y0 = y0.detach().contiguous()
         if ode.uncertainty == "bayes":
             mus, sds = ode.ude_mean_std()
-            eps = ode.take_eps(4 * plan.prob.n_steps, sum(int(p.numel()) for p in mus), dev).contiguous()
-            mus = [p.detach().contiguous() for p in mus]
-            sds = [p.detach().contiguous() for p in sds]
-            pack = torch.empty(max(sz.pack_bytes // 4, 1), dtype=torch.float32, device=dev)
-            plan.lib.pack_bayes(plan.desc, plan.prob, [w.data_ptr() for w in mus[0::2]],
-                                [b.data_ptr() for b in mus[1::2]], [w.data_ptr() for w in sds[0::2]],
-                                [b.data_ptr() for b in sds[1::2]], eps.data_ptr(), pack.data_ptr(), stream)
+            eps = ode.take_eps(4 * plan.prob.n_steps, sum(int(p.numel()) for p in mus), dev)
+            pack = _fused._bayes_pack(plan, mus, sds, eps, dev)
         else:
             params = []
             for lin in ode.ude_linears():
@@ -229,12 +221,9 @@ def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
         yhat = torch.empty((plan.n_times, N, R), dtype=torch.float32, device=dev)
         stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
         stats, sums, st = _fused._stats_out(plan, dev)
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
-        plan.lib.forecast_dec(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                              dec_pack.data_ptr(), yhat.data_ptr(), stats_slab.data_ptr(),
-                              _fused._ctl(plan, dev).data_ptr(), st, stream)
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("forecast_dec", e0, e1))
+        with _fused._timed("forecast_dec"):
+            plan.lib.forecast_dec(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                                  dec_pack.data_ptr(), yhat.data_ptr(), stats_slab.data_ptr(),
+                                  _fused._ctl(plan, dev).data_ptr(), st, stream)
         ode._record_fused(stats, plan.n_eval, sums=sums)
     return yhat

@@ -7,6 +7,7 @@ PyTorch only provides device memory and the current HIP stream here.
 """
 from __future__ import annotations
 
+from contextlib import contextmanager
 from dataclasses import dataclass, field
 from typing import Dict, List, Optional, Tuple
 import weakref
@@ -98,8 +99,19 @@ def make_plan(cfg, schedule: Schedule, n_traj: int, fa_w: float, device: torch.d
 EVENTS = None
 
 
-def _ev(dev):
-    return torch.cuda.Event(enable_timing=True)
+@contextmanager
+def _timed(kind: str):
+    """Brackets one C-ABI call: when ``EVENTS`` is a list, appends (kind, start_event, end_event),
+    recorded on the current stream right before and right after the call."""
+    if EVENTS is None:
+        yield
+        return
+    e0 = torch.cuda.Event(enable_timing=True)
+    e0.record()
+    yield
+    e1 = torch.cuda.Event(enable_timing=True)
+    e1.record()
+    EVENTS.append((kind, e0, e1))
 
 
 def _ptr(t: Optional[torch.Tensor]) -> Optional[int]:
@@ -198,6 +210,21 @@ def invalidate_packs() -> None:
         plan.pack_key, plan.pack = None, None
 
 
+def _bayes_pack(plan: Plan, mus, sds, eps: torch.Tensor, dev) -> torch.Tensor:
+    """The pack of a Bayesian model (ude_pack_weights_bayes): every evaluation's weight sample
+    w_e = mean + eps_e |std| in fragment order, then eps in slab order.  mus / sds: the means and the
+    raw stds (w, b per layer, torch order); eps: the solve's (4 n_steps, n_params) draws.  Packed on
+    every call: the draws differ from solve to solve."""
+    mus = [p.contiguous() for p in mus]
+    sds = [p.contiguous() for p in sds]
+    eps = eps.contiguous()
+    pack = torch.empty(max(plan.sizes.pack_bytes // 4, 1), dtype=torch.float32, device=dev)
+    plan.lib.pack_bayes(plan.desc, plan.prob, [w.data_ptr() for w in mus[0::2]], [b.data_ptr() for b in mus[1::2]],
+                        [w.data_ptr() for w in sds[0::2]], [b.data_ptr() for b in sds[1::2]], eps.data_ptr(),
+                        pack.data_ptr(), _stream(dev))
+    return pack
+
+
 _ZEROS = {}
 
 
@@ -245,22 +272,9 @@ class FusedRK4(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan: Plan, y0: torch.Tensor, keep_ckpt: bool, *params: torch.Tensor):
         dev = y0.device
-        stream = _stream(dev)
-        sz = plan.sizes
         pack = packed_weights(plan, params, dev)
-        latent = torch.empty((plan.n_times,) + tuple(y0.shape), dtype=torch.float32, device=dev)
         need_grad = any(ctx.needs_input_grad[1:])
-        ckpt = torch.empty(max(sz.ckpt_bytes // 4, 1), dtype=torch.float32, device=dev) \
-            if (need_grad or keep_ckpt) else None
-        stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
-        stats, sums, st = _stats_out(plan, dev)
-        if EVENTS is not None:
-            e0 = _ev(dev); e0.record()
-        plan.lib.forward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                            latent.data_ptr(), _ptr(ckpt), stats_slab.data_ptr(), _ctl(plan, dev).data_ptr(), st,
-                            stream)
-        if EVENTS is not None:
-            e1 = _ev(dev); e1.record(); EVENTS.append(("fwd", e0, e1))
+        latent, stats, ckpt, sums = _solve_forward(plan, y0, pack, need_grad or keep_ckpt)
         ctx.plan = plan
         ctx.set_materialize_grads(False)
         if need_grad:
@@ -274,7 +288,6 @@ class FusedRK4(torch.autograd.Function):
         plan: Plan = ctx.plan
         y0, pack, ckpt, *stats = ctx.saved_tensors
         dev = y0.device
-        stream = _stream(dev)
         if dl3 is not None and _is_placeholder(dl3):
             dl3 = None
         if dl3 is not None:
@@ -289,18 +302,38 @@ class FusedRK4(torch.autograd.Function):
                 dlatent = dlatent.clone()
                 dlatent[..., :3] += dl3
                 dl3 = None
-        dst, _keep = _dstats(dmean, dstd, dnorm)
-        dy0 = torch.empty_like(y0)
-        slab = torch.empty(max(plan.sizes.grad_slab_bytes // 4, 1), dtype=torch.float32, device=dev)
-        dparams = torch.empty(plan.sizes.n_params, dtype=torch.float32, device=dev)
-        if EVENTS is not None:
-            e0 = _ev(dev); e0.record()
-        plan.lib.backward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                             ckpt.data_ptr(), _ptr(dlatent), _ptr(dl3), _stats_in(stats), dst, dy0.data_ptr(),
-                             slab.data_ptr(), _ctl(plan, dev).data_ptr(), dparams.data_ptr(), stream)
-        if EVENTS is not None:
-            e1 = _ev(dev); e1.record(); EVENTS.append(("bwd", e0, e1))
+        dy0, dparams = _solve_backward(plan, y0, pack, ckpt, stats, dlatent, dl3, (dmean, dstd, dnorm))
         return (None, dy0, None) + tuple(_split(dparams, plan.param_shapes))
+
+
+def _solve_forward(plan: Plan, y0: torch.Tensor, pack: torch.Tensor, want_ckpt: bool):
+    """ude_rk4_forward_ex on a packed model: (latent, stats, training store or None, fp64 sums)."""
+    dev = y0.device
+    sz = plan.sizes
+    latent = torch.empty((plan.n_times,) + tuple(y0.shape), dtype=torch.float32, device=dev)
+    ckpt = torch.empty(max(sz.ckpt_bytes // 4, 1), dtype=torch.float32, device=dev) if want_ckpt else None
+    stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
+    stats, sums, st = _stats_out(plan, dev)
+    with _timed("fwd"):
+        plan.lib.forward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                            latent.data_ptr(), _ptr(ckpt), stats_slab.data_ptr(), _ctl(plan, dev).data_ptr(), st,
+                            _stream(dev))
+    return latent, stats, ckpt, sums
+
+
+def _solve_backward(plan: Plan, y0, pack, ckpt, stats, dlatent, dl3, dstats):
+    """ude_rk4_backward_ex: (dy0, flat d params) for the full cotangent ``dlatent`` or the compact S, I, R
+    one ``dl3`` (contiguous fp32, exactly one of them) and the statistics' cotangents ``dstats``."""
+    dev = y0.device
+    dst, _keep = _dstats(*dstats)
+    dy0 = torch.empty_like(y0)
+    slab = torch.empty(max(plan.sizes.grad_slab_bytes // 4, 1), dtype=torch.float32, device=dev)
+    dparams = torch.empty(plan.sizes.n_params, dtype=torch.float32, device=dev)
+    with _timed("bwd"):
+        plan.lib.backward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                             _ptr(ckpt), _ptr(dlatent), _ptr(dl3), _stats_in(stats), dst, dy0.data_ptr(),
+                             slab.data_ptr(), _ctl(plan, dev).data_ptr(), dparams.data_ptr(), _stream(dev))
+    return dy0, dparams
 
 
 class FusedRK4Dec(torch.autograd.Function):
@@ -344,20 +377,12 @@ class FusedBayesRK4Dec(torch.autograd.Function):
     def forward(ctx, plan: Plan, y0: torch.Tensor, eps: torch.Tensor, Wd: torch.Tensor, bd: torch.Tensor,
                 *params: torch.Tensor):
         dev = y0.device
-        stream = _stream(dev)
-        sz = plan.sizes
         k = len(params) // 2
-        mus = [p.contiguous() for p in params[:k]]
-        sds = [p.contiguous() for p in params[k:]]
-        eps = eps.contiguous()
-        pack = torch.empty(max(sz.pack_bytes // 4, 1), dtype=torch.float32, device=dev)
-        plan.lib.pack_bayes(plan.desc, plan.prob, [w.data_ptr() for w in mus[0::2]], [b.data_ptr() for b in mus[1::2]],
-                            [w.data_ptr() for w in sds[0::2]], [b.data_ptr() for b in sds[1::2]], eps.data_ptr(),
-                            pack.data_ptr(), stream)
+        pack = _bayes_pack(plan, params[:k], params[k:], eps, dev)
         yhat, reg, stats, ckpt, sums = _dec_forward(plan, y0, pack, Wd, bd)
         ctx.plan = plan
         ctx.set_materialize_grads(False)
-        ctx.save_for_backward(y0, pack, ckpt, Wd.contiguous(), *stats, *sds)
+        ctx.save_for_backward(y0, pack, ckpt, Wd.contiguous(), *stats, *params[k:])
         ctx.mark_non_differentiable(ckpt, sums)
         token = zero_grad_like(torch.empty((plan.n_times,) + tuple(y0.shape), device="meta"), dev)
         return (yhat, reg[0]) + stats + (token, ckpt, sums)
@@ -390,20 +415,16 @@ def _dec_forward(plan: Plan, y0: torch.Tensor, pack: torch.Tensor, Wd: torch.Ten
     reg_slab = torch.empty(max(sz.grid_fwd, 1), dtype=torch.float64, device=dev)
     stats, sums, st = _stats_out(plan, dev)
     reg = torch.empty(1, dtype=torch.float32, device=dev)
-    if EVENTS is not None:
-        e0 = _ev(dev); e0.record()
-    plan.lib.forward_dec_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                            dec_pack.data_ptr(), yhat.data_ptr(), ckpt.data_ptr(), stats_slab.data_ptr(),
-                            reg_slab.data_ptr(), _ctl(plan, dev).data_ptr(), st, reg.data_ptr(), stream)
-    if EVENTS is not None:
-        e1 = _ev(dev); e1.record(); EVENTS.append(("fwd_dec", e0, e1))
+    with _timed("fwd_dec"):
+        plan.lib.forward_dec_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                                dec_pack.data_ptr(), yhat.data_ptr(), ckpt.data_ptr(), stats_slab.data_ptr(),
+                                reg_slab.data_ptr(), _ctl(plan, dev).data_ptr(), st, reg.data_ptr(), stream)
     return yhat, reg, stats, ckpt, sums
 
 
 def _dec_backward(plan: Plan, y0, pack, ckpt, stats, Wd, dyhat, dreg, dstats, dlatent):
     """ude_decoder_backward then ude_rk4_backward_sir: (dy0, d W_dec, d b_dec, flat d params)."""
     dev = y0.device
-    stream = _stream(dev)
     sz = plan.sizes
     N, R, L = y0.shape
     T = plan.n_times
@@ -415,30 +436,17 @@ def _dec_backward(plan: Plan, y0, pack, ckpt, stats, Wd, dyhat, dreg, dstats, dl
     dWd = torch.empty_like(Wd)
     dbd = torch.empty(R, dtype=torch.float32, device=dev)
     dec_ws = torch.empty(max(sz.dec_ws_bytes // 4, 1), dtype=torch.float32, device=dev)
-    if EVENTS is not None:
-        e0 = _ev(dev); e0.record()
-    plan.lib.decoder_backward(plan.desc, plan.prob, plan.sched_dev.data_ptr(), ckpt.data_ptr(), dyhat.data_ptr(),
-                              Wd.data_ptr(), g_reg.data_ptr(), dec_ws.data_ptr(), dl3.data_ptr(), dWd.data_ptr(),
-                              dbd.data_ptr(), stream)
-    if EVENTS is not None:
-        e1 = _ev(dev); e1.record(); EVENTS.append(("dec_bwd", e0, e1))
+    with _timed("dec_bwd"):
+        plan.lib.decoder_backward(plan.desc, plan.prob, plan.sched_dev.data_ptr(), ckpt.data_ptr(), dyhat.data_ptr(),
+                                  Wd.data_ptr(), g_reg.data_ptr(), dec_ws.data_ptr(), dl3.data_ptr(), dWd.data_ptr(),
+                                  dbd.data_ptr(), _stream(dev))
     full = None
     if dlatent is not None and not _is_placeholder(dlatent):
         # the materialised latent was used too: one full cotangent
         full = dlatent.contiguous().to(torch.float32).clone()
         full[..., :3] += dl3
         dl3 = None
-    dst, _keep = _dstats(*dstats)
-    dy0 = torch.empty_like(y0)
-    slab = torch.empty(max(sz.grad_slab_bytes // 4, 1), dtype=torch.float32, device=dev)
-    dparams = torch.empty(sz.n_params, dtype=torch.float32, device=dev)
-    if EVENTS is not None:
-        e0 = _ev(dev); e0.record()
-    plan.lib.backward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                         ckpt.data_ptr(), _ptr(full), _ptr(dl3), _stats_in(stats), dst, dy0.data_ptr(),
-                         slab.data_ptr(), _ctl(plan, dev).data_ptr(), dparams.data_ptr(), stream)
-    if EVENTS is not None:
-        e1 = _ev(dev); e1.record(); EVENTS.append(("bwd", e0, e1))
+    dy0, dparams = _solve_backward(plan, y0, pack, ckpt, stats, full, dl3, dstats)
     return dy0, dWd, dbd, dparams
 
 
@@ -533,33 +541,14 @@ class FusedBayesRK4(torch.autograd.Function):
     @staticmethod
     def forward(ctx, plan: Plan, y0: torch.Tensor, eps: torch.Tensor, keep_ckpt: bool, *params: torch.Tensor):
         dev = y0.device
-        stream = _stream(dev)
-        sz = plan.sizes
         k = len(params) // 2
-        mus = [p.contiguous() for p in params[:k]]
-        sds = [p.contiguous() for p in params[k:]]
-        eps = eps.contiguous()
-        pack = torch.empty(max(sz.pack_bytes // 4, 1), dtype=torch.float32, device=dev)
-        plan.lib.pack_bayes(plan.desc, plan.prob, [w.data_ptr() for w in mus[0::2]], [b.data_ptr() for b in mus[1::2]],
-                            [w.data_ptr() for w in sds[0::2]], [b.data_ptr() for b in sds[1::2]], eps.data_ptr(),
-                            pack.data_ptr(), stream)
-        latent = torch.empty((plan.n_times,) + tuple(y0.shape), dtype=torch.float32, device=dev)
+        pack = _bayes_pack(plan, params[:k], params[k:], eps, dev)
         need_grad = any(ctx.needs_input_grad[1:])
-        ckpt = torch.empty(max(sz.ckpt_bytes // 4, 1), dtype=torch.float32, device=dev) \
-            if (need_grad or keep_ckpt) else None
-        stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
-        stats, sums, st = _stats_out(plan, dev)
-        if EVENTS is not None:
-            e0 = _ev(dev); e0.record()
-        plan.lib.forward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                            latent.data_ptr(), _ptr(ckpt), stats_slab.data_ptr(), _ctl(plan, dev).data_ptr(), st,
-                            stream)
-        if EVENTS is not None:
-            e1 = _ev(dev); e1.record(); EVENTS.append(("fwd", e0, e1))
+        latent, stats, ckpt, sums = _solve_forward(plan, y0, pack, need_grad or keep_ckpt)
         ctx.plan = plan
         ctx.set_materialize_grads(False)
         if need_grad:
-            ctx.save_for_backward(y0, pack, ckpt, *stats, *sds)
+            ctx.save_for_backward(y0, pack, ckpt, *stats, *params[k:])
         out_ck = ckpt if keep_ckpt else torch.empty(0, dtype=torch.float32, device=dev)
         ctx.mark_non_differentiable(out_ck, sums)
         return (latent,) + stats + (out_ck, sums)
@@ -570,21 +559,10 @@ class FusedBayesRK4(torch.autograd.Function):
         y0, pack, ckpt, *rest = ctx.saved_tensors
         stats, sds = rest[:3], rest[3:]
         dev = y0.device
-        stream = _stream(dev)
         if dlatent is None or _is_placeholder(dlatent):
             dlatent = torch.zeros((plan.n_times,) + tuple(y0.shape), dtype=torch.float32, device=dev)
         dlatent = dlatent.contiguous().to(torch.float32)
-        dst, _keep = _dstats(dmean, dstd, dnorm)
-        dy0 = torch.empty_like(y0)
-        slab = torch.empty(max(plan.sizes.grad_slab_bytes // 4, 1), dtype=torch.float32, device=dev)
-        dparams = torch.empty(plan.sizes.n_params, dtype=torch.float32, device=dev)
-        if EVENTS is not None:
-            e0 = _ev(dev); e0.record()
-        plan.lib.backward_ex(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                             _ptr(ckpt), dlatent.data_ptr(), None, _stats_in(stats), dst, dy0.data_ptr(),
-                             slab.data_ptr(), _ctl(plan, dev).data_ptr(), dparams.data_ptr(), stream)
-        if EVENTS is not None:
-            e1 = _ev(dev); e1.record(); EVENTS.append(("bwd", e0, e1))
+        dy0, dparams = _solve_backward(plan, y0, pack, ckpt, stats, dlatent, None, (dmean, dstd, dnorm))
         n = plan.sizes.n_params // 2
         d_mu = _split(dparams[:n], plan.param_shapes)
         d_sd = _split(_d_std(dparams[n:], sds), plan.param_shapes)

@@ -29,12 +29,9 @@ class _LossHead(torch.autograd.Function):
         ws = torch.empty(max(nbytes // 8, 1), dtype=torch.float64, device=dev)
         out = torch.empty(2, dtype=torch.float32, device=dev)
         latent, W, b, y = latent.contiguous(), W.contiguous(), b.contiguous(), y.contiguous()
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
-        lib.loss_forward(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(), ws.data_ptr(),
-                         out.data_ptr(), stream)
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("loss_fwd", e0, e1))
+        with _fused._timed("loss_fwd"):
+            lib.loss_forward(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(),
+                             ws.data_ptr(), out.data_ptr(), stream)
         ctx.meta = (lib, desc, T, S, B)
         # a latent straight from the fused solve takes its (S, I, R-only) cotangent compactly,
         # as the gradient of the solve's sir_token output (fused.sir_token_like)
@@ -59,22 +56,19 @@ class _LossHead(torch.autograd.Function):
                             zero if g_reg is None else g_reg.float().reshape(())])
         dW = torch.empty_like(W)
         db = torch.empty_like(b)
-        if _fused.EVENTS is not None:
-            e0 = _fused._ev(dev); e0.record()
         dl3 = dlat = None
-        if compact:
-            N, R = latent.shape[1], latent.shape[2]
-            dl3 = torch.empty((T, N, R, 3), dtype=torch.float32, device=dev)
-            lib.loss_backward_sir(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(),
-                                  grad.data_ptr(), ws.data_ptr(), dl3.data_ptr(), dW.data_ptr(), db.data_ptr(),
+        with _fused._timed("loss_bwd"):
+            if compact:
+                N, R = latent.shape[1], latent.shape[2]
+                dl3 = torch.empty((T, N, R, 3), dtype=torch.float32, device=dev)
+                lib.loss_backward_sir(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(),
+                                      grad.data_ptr(), ws.data_ptr(), dl3.data_ptr(), dW.data_ptr(), db.data_ptr(),
+                                      _fused._stream(dev))
+            else:
+                dlat = torch.empty_like(latent)
+                lib.loss_backward(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(),
+                                  grad.data_ptr(), ws.data_ptr(), dlat.data_ptr(), dW.data_ptr(), db.data_ptr(),
                                   _fused._stream(dev))
-        else:
-            dlat = torch.empty_like(latent)
-            lib.loss_backward(desc, T, S, B, latent.data_ptr(), W.data_ptr(), b.data_ptr(), y.data_ptr(),
-                              grad.data_ptr(), ws.data_ptr(), dlat.data_ptr(), dW.data_ptr(), db.data_ptr(),
-                              _fused._stream(dev))
-        if _fused.EVENTS is not None:
-            e1 = _fused._ev(dev); e1.record(); _fused.EVENTS.append(("loss_bwd", e0, e1))
         return None, None, None, None, None, dlat, dl3, dW, db, None
 
 

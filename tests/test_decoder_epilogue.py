@@ -170,7 +170,7 @@ def test_epilogue_chain_matches_fp64(pkg, name):
     assert plan.prob.recompute == 0
     if name == "FaFp_R49_split":
         # the launch training takes at this size: stored activations, one tile per CU at the most
-        # (ude_entry.h forward_dec: SPLIT_FWD && n_tiles <= CUs -> the 8-wave kernel)
+        # (ude_entry.h launch_forward: SPLIT_FWD && n_tiles <= CUs -> the 8-wave kernel)
         assert plan.sizes.act_bytes > 0
         assert _n_tiles(case) <= torch.cuda.get_device_properties(0).multi_processor_count
     assert tuple(out["stats"].shape) == (T, case.B, case.mod.n_regions, 2)
