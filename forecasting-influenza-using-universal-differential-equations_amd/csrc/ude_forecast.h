@@ -12,6 +12,13 @@
 // each t in a fixed order (no atomics: the same bits run to run).  grid.y is t, so no workgroup
 // straddles two time indices.  Everything after the load is fp64: the difference of two normal CDFs
 // and its == 0 floor agree with SciPy's only there, and the work is one group per (t, b, r).
+//
+// The VERIFY variant (ude_forecast_verify) scores the ensemble itself from the same, always sorted,
+// tile: CRPS, the weighted interval score, interval coverage, the PIT bin of the target's mid-rank
+// and the empirical mass of the multibin window.  Per-day values go through per-workgroup partials
+// as above; per-region values through a per-group terms scratch that a second kernel sums over b.
+// The body is one template: the instantiation behind ude_forecast_summary has no VERIFY code, and
+// the VERIFY one runs the shared code first, so the six shared outputs have the same bits.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -23,6 +30,11 @@ constexpr int FC_THREADS = 256;
 constexpr int FC_TILE_ELEMS = 4096;      // [S][G] doubles: 32 KiB, four workgroups per CU by LDS
 constexpr int FC_MAX_G = 64;
 constexpr int FC_MAX_SQ = 1024;          // largest S with quantiles (the sorted tile)
+constexpr int FC_MAX_ALPHA = 16;         // interval levels of the weighted interval score
+constexpr int FC_MAX_PIT = 64;           // PIT histogram bins
+constexpr int FC_TERMS = 7;              // per-group terms: nll, log mass, |y - mean|, crps, wis, log
+                                         // empirical mass, coverage bits (bit k: interval k holds y)
+constexpr int FC_DEAD_BIN = 255;         // PIT bin of a column past B R
 
 struct FcGeom {
   int rows;      // tile rows: S, or its power-of-two padding when sorting; 0 = no tile (S too large)
@@ -58,6 +70,13 @@ struct FcArgs {
   int T, S, B, R, n_q;
 };
 
+struct FcVerifyArgs {
+  const double* alpha; // [K] interval levels in (0, 1)
+  double* vpart;       // [T][nbx][3 + K + J]: crps, wis, log empirical mass, K coverage and J PIT counts
+  double* terms;       // [T][FC_TERMS][B R]
+  int K, J;
+};
+
 // scipy.special.ndtr's branches (cephes ndtr.c) on the fp64 erf / erfc
 __device__ __forceinline__ double fc_ndtr(double a) {
   const double x = a * 0.70710678118654752440, z = fabs(x);
@@ -78,10 +97,34 @@ __device__ __forceinline__ double fc_col_sum(double* red, double v, int rr, int 
   return red[c];
 }
 
-__global__ __launch_bounds__(FC_THREADS) void ude_forecast_summary_kernel(FcArgs a) {
+// numpy.quantile, method 'linear' (numpy/lib/function_base.py _lerp), of the S sorted rows of column c
+__device__ __forceinline__ double fc_quantile(const double* tile, int c, int G, int S, double q) {
+  const double h = (double)(S - 1) * q;
+  int lo = (int)floor(h);
+  if (lo < 0) lo = 0;
+  if (lo > S - 1) lo = S - 1;
+  const int hi = lo + 1 < S ? lo + 1 : S - 1;
+  const double gm = h - (double)lo, x = tile[lo * G + c], y = tile[hi * G + c], d = y - x;
+  return gm >= 0.5 ? y - d * (1.0 - gm) : x + d * gm;
+}
+
+// how many of the S sorted rows of column c are < x (LE: <= x); the +inf padding rows are never read
+template <bool LE>
+__device__ __forceinline__ int fc_count_below(const double* tile, int c, int G, int S, double x) {
+  int lo = 0, hi = S;
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    const double v = tile[mid * G + c];
+    if (LE ? v <= x : v < x) lo = mid + 1; else hi = mid;
+  }
+  return lo;
+}
+
+template <bool VERIFY>
+__device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyArgs& v) {
   extern __shared__ __attribute__((aligned(16))) double fc_lds[];
   const int BR = a.B * a.R;
-  const FcGeom ge = fc_geom(a.S, BR, a.n_q);
+  const FcGeom ge = fc_geom(a.S, BR, VERIFY ? 1 : a.n_q);   // VERIFY always sorts
   const int G = ge.G, RP = FC_THREADS / G, rows = ge.rows;
   double* red = fc_lds;                          // [RP][G] = 256 doubles
   double* tile = fc_lds + FC_THREADS;            // [rows][G]
@@ -117,7 +160,7 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_summary_kernel(FcArgs
     a.std[o] = sd;
   }
 
-  if (a.n_q > 0) {
+  if (VERIFY || a.n_q > 0) {
     // bitonic network along S: rows / 2 compare-exchanges per column and stage over all threads
     const int half = rows >> 1;
     for (int k = 2; k <= rows; k <<= 1) {
@@ -136,16 +179,8 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_summary_kernel(FcArgs
     }
     __syncthreads();
     if (live) {
-      for (int k = rr; k < a.n_q; k += RP) {
-        // numpy.quantile, method 'linear' (numpy/lib/function_base.py _lerp)
-        const double h = (double)(a.S - 1) * a.q[k];
-        int lo = (int)floor(h);
-        if (lo < 0) lo = 0;
-        if (lo > a.S - 1) lo = a.S - 1;
-        const int hi = lo + 1 < a.S ? lo + 1 : a.S - 1;
-        const double gm = h - (double)lo, x = tile[lo * G + c], y = tile[hi * G + c], d = y - x;
-        a.quant[(((size_t)k * a.B + b) * a.T + t) * a.R + r] = gm >= 0.5 ? y - d * (1.0 - gm) : x + d * gm;
-      }
+      for (int k = rr; k < a.n_q; k += RP)
+        a.quant[(((size_t)k * a.B + b) * a.T + t) * a.R + r] = fc_quantile(tile, c, G, a.S, a.q[k]);
     }
   }
 
@@ -171,7 +206,86 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_summary_kernel(FcArgs
       for (int i = 0; i < G; ++i) s += red[tid * G + i];
       a.part[((size_t)t * gridDim.x + blockIdx.x) * 3 + tid] = s;
     }
+    if constexpr (VERIFY) {
+      if (live && rr == 0) {
+        double* tg = v.terms + (size_t)t * FC_TERMS * BR + g;
+        tg[0] = t0;
+        tg[(size_t)BR] = t1;
+        tg[(size_t)2 * BR] = t2;
+      }
+    }
   }
+
+  if constexpr (VERIFY) {
+    // the ensemble's own scores from the sorted tile (targets are given: checked by the host)
+    const double y = live ? (double)a.y_true[o] * sc : 0.0, dS = (double)a.S;
+    double w = 0.0, ad = 0.0;
+    for (int i = rr; i < a.S; i += RP) {
+      const double x = tile[i * G + c];
+      w += (double)(2 * i - a.S + 1) * x;
+      ad += fabs(x - y);
+    }
+    const double wsum = fc_col_sum(red, w, rr, c, G, RP);
+    const double asum = fc_col_sum(red, ad, rr, c, G, RP);
+    double iv = 0.0, bits = 0.0;                   // interval k of thread row k mod RP
+    for (int k = rr; k < v.K; k += RP) {
+      const double al = v.alpha[k];
+      const double l = fc_quantile(tile, c, G, a.S, 0.5 * al), u = fc_quantile(tile, c, G, a.S, 1.0 - 0.5 * al);
+      iv += 0.5 * al * ((u - l) + (2.0 / al) * fmax(l - y, 0.0) + (2.0 / al) * fmax(y - u, 0.0));
+      if (l <= y && y <= u) bits += (double)(1 << k);
+    }
+    const double ivsum = fc_col_sum(red, iv, rr, c, G, RP);
+    const double cover = fc_col_sum(red, bits, rr, c, G, RP);   // distinct bits: the sum is their union
+    double t3 = 0.0, t4 = 0.0, t5 = 0.0, packed = (double)(FC_DEAD_BIN << 16);
+    if (live && rr == 0) {
+      t3 = asum / dS - wsum / (dS * dS);
+      t4 = (0.5 * fabs(y - fc_quantile(tile, c, G, a.S, 0.5)) + ivsum) / ((double)v.K + 0.5);
+      const int n_lt = fc_count_below<false>(tile, c, G, a.S, y), n_le = fc_count_below<true>(tile, c, G, a.S, y);
+      int bin = (v.J * (n_lt + n_le)) / (2 * a.S);
+      if (bin > v.J - 1) bin = v.J - 1;
+      const double cb = floor(y * 10.0) / 10.0;
+      const int n_win = fc_count_below<false>(tile, c, G, a.S, cb + 0.6) -
+                        fc_count_below<false>(tile, c, G, a.S, cb - 0.5);
+      t5 = log(n_win == 0 ? 4.5399929762484854e-05 : (double)n_win / dS);
+      packed = cover + (double)(bin << 16);
+      double* tg = v.terms + ((size_t)t * FC_TERMS + 3) * BR + g;
+      tg[0] = t3;
+      tg[(size_t)BR] = t4;
+      tg[(size_t)2 * BR] = t5;
+      tg[(size_t)3 * BR] = cover;
+    }
+    __syncthreads();
+    if (rr == 0) {
+      red[c] = t3;
+      red[G + c] = t4;
+      red[2 * G + c] = t5;
+      red[3 * G + c] = packed;
+    }
+    __syncthreads();
+    const int NP = 3 + v.K + v.J;
+    if (tid < NP) {
+      double s = 0.0;
+      if (tid < 3) {
+        for (int i = 0; i < G; ++i) s += red[tid * G + i];
+      } else {
+        int n = 0;
+        for (int i = 0; i < G; ++i) {
+          const unsigned pk = (unsigned)red[3 * G + i];
+          n += tid < 3 + v.K ? (pk >> (tid - 3)) & 1u : (pk >> 16) == (unsigned)(tid - 3 - v.K);
+        }
+        s = (double)n;
+      }
+      v.vpart[((size_t)t * gridDim.x + blockIdx.x) * NP + tid] = s;
+    }
+  }
+}
+
+__global__ __launch_bounds__(FC_THREADS) void ude_forecast_summary_kernel(FcArgs a) {
+  fc_summary_body<false>(a, FcVerifyArgs{});
+}
+
+__global__ __launch_bounds__(FC_THREADS) void ude_forecast_verify_kernel(FcArgs a, FcVerifyArgs v) {
+  fc_summary_body<true>(a, v);
 }
 
 // scores[k][t] = (sum over the workgroups of t, lane-strided then a fixed butterfly) / (B R)
@@ -184,6 +298,48 @@ __global__ __launch_bounds__(64) void ude_forecast_scores_kernel(const double* _
 #pragma unroll
     for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
     if (ln == 0) scores[(size_t)k * T + t] = s * inv_n;
+  }
+}
+
+// The VERIFY outputs, one workgroup of FC_TERMS waves per (64 regions, t); wave f takes term f.
+// vreg[f][t][r] = the sum over b = 0 .. B-1, in that order, of the group terms / B: f < 6 the six scores,
+// 6 + k the coverage of interval k (an integer count, divided once).  The first workgroup of each t also
+// forms vday[k][t] = (sum over the workgroup partials of t, as ude_forecast_scores_kernel sums them) /
+// (B R), k < 3 + K + J, wave f those with k = f mod FC_TERMS.
+__global__ __launch_bounds__(64 * FC_TERMS) void ude_forecast_verify_reduce_kernel(
+    const double* __restrict__ vpart, const double* __restrict__ terms, int nbx, int T, int B, int R, int K, int J,
+    double* __restrict__ vday, double* __restrict__ vreg) {
+  const int t = blockIdx.y, ln = threadIdx.x, f = threadIdx.y;
+  const size_t BR = (size_t)B * R;
+  if (blockIdx.x == 0) {
+    const int NP = 3 + K + J;
+    for (int k = f; k < NP; k += FC_TERMS) {
+      double s = 0.0;
+      for (int i = ln; i < nbx; i += 64) s += vpart[((size_t)t * nbx + i) * NP + k];
+#pragma unroll
+      for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+      if (ln == 0) vday[(size_t)k * T + t] = s / (double)BR;
+    }
+  }
+  const int r = blockIdx.x * 64 + ln;
+  if (r >= R) return;
+  const double* p = terms + ((size_t)t * FC_TERMS + f) * BR + r;
+  if (f < 6) {
+    double acc = 0.0;
+#pragma unroll 8
+    for (int b = 0; b < B; ++b) acc += p[(size_t)b * R];
+    vreg[((size_t)f * T + t) * R + r] = acc / (double)B;
+  } else {
+    int cnt[FC_MAX_ALPHA] = {};
+#pragma unroll 8
+    for (int b = 0; b < B; ++b) {
+      const unsigned bits = (unsigned)p[(size_t)b * R];
+#pragma unroll
+      for (int k = 0; k < FC_MAX_ALPHA; ++k) cnt[k] += (bits >> k) & 1u;
+    }
+#pragma unroll
+    for (int k = 0; k < FC_MAX_ALPHA; ++k)
+      if (k < K) vreg[((size_t)(6 + k) * T + t) * R + r] = (double)cnt[k] / (double)B;
   }
 }
 
@@ -218,6 +374,45 @@ inline int forecast_summary(int T, int S, int B, int R, const float* yhat, const
                        1.0 / ((double)B * (double)R), scores);
     if (hipGetLastError() != hipSuccess) return -3;
   }
+  return 0;
+}
+
+inline bool fc_verify_ok(int T, int S, int B, int R, int n_q, int K, int J) {
+  return fc_shape_ok(T, S, B, R, n_q) && S <= FC_MAX_SQ && K >= 1 && K <= FC_MAX_ALPHA && J >= 1 && J <= FC_MAX_PIT;
+}
+
+// workspace: part [T][nbx][3] | vpart [T][nbx][3 + K + J] | terms [T][FC_TERMS][B R], doubles
+inline int forecast_verify_workspace(int T, int S, int B, int R, int n_q, int K, int J, int64_t* ws_bytes) {
+  if (!ws_bytes || !fc_verify_ok(T, S, B, R, n_q, K, J)) return -2;
+  const int64_t nbx = fc_geom(S, B * R, 1).nbx;
+  *ws_bytes = ((int64_t)T * nbx * (6 + K + J) + (int64_t)T * FC_TERMS * B * R) * 8;
+  return 0;
+}
+
+inline int forecast_verify(int T, int S, int B, int R, const float* yhat, const double* scale, const float* y_true,
+                           const double* q, int n_q, const double* alpha, int K, int J, void* ws, double* mean,
+                           double* std, double* quant, double* scores, double* vday, double* vreg, hipStream_t s) {
+  if (!fc_verify_ok(T, S, B, R, n_q, K, J) || !yhat || !mean || !std) return -2;
+  if (n_q > 0 && (!q || !quant)) return -2;
+  if (!y_true || !alpha || !ws || !scores || !vday || !vreg) return -2;
+  const FcGeom ge = fc_geom(S, B * R, 1);
+  FcArgs a;
+  a.yhat = yhat; a.scale = scale; a.y_true = y_true; a.q = q;
+  a.mean = mean; a.std = std; a.quant = quant; a.part = (double*)ws;
+  a.T = T; a.S = S; a.B = B; a.R = R; a.n_q = n_q;
+  FcVerifyArgs v;
+  v.alpha = alpha; v.K = K; v.J = J;
+  v.vpart = a.part + (size_t)T * ge.nbx * 3;
+  v.terms = v.vpart + (size_t)T * ge.nbx * (3 + K + J);
+  const size_t lds = ((size_t)FC_THREADS + (size_t)ge.rows * ge.G) * 8;
+  hipLaunchKernelGGL(ude_forecast_verify_kernel, dim3(ge.nbx, T), dim3(FC_THREADS), lds, s, a, v);
+  if (hipGetLastError() != hipSuccess) return -3;
+  hipLaunchKernelGGL(ude_forecast_scores_kernel, dim3(T), dim3(64), 0, s, (const double*)ws, ge.nbx, T,
+                     1.0 / ((double)B * (double)R), scores);
+  if (hipGetLastError() != hipSuccess) return -3;
+  hipLaunchKernelGGL(ude_forecast_verify_reduce_kernel, dim3((R + 63) / 64, T), dim3(64, FC_TERMS), 0, s,
+                     (const double*)v.vpart, (const double*)v.terms, ge.nbx, T, B, R, K, J, vday, vreg);
+  if (hipGetLastError() != hipSuccess) return -3;
   return 0;
 }
 

@@ -304,6 +304,19 @@ int ude_forecast_summary(int32_t T, int32_t S, int32_t B, int32_t R, const float
                                (hipStream_t)stream);
 }
 
+int ude_forecast_verify_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int32_t n_alpha,
+                                  int32_t n_pit, int64_t* ws_bytes) {
+  return ude::forecast_verify_workspace(T, S, B, R, n_q, n_alpha, n_pit, ws_bytes);
+}
+
+int ude_forecast_verify(int32_t T, int32_t S, int32_t B, int32_t R, const float* yhat, const double* scale,
+                        const float* y_true, const double* q, int32_t n_q, const double* alpha, int32_t n_alpha,
+                        int32_t n_pit, void* ws, double* mean, double* std, double* quant, double* scores,
+                        double* day, double* region, ude_stream_t stream) {
+  return ude::forecast_verify(T, S, B, R, yhat, scale, y_true, q, n_q, alpha, n_alpha, n_pit, ws, mean, std, quant,
+                              scores, day, region, (hipStream_t)stream);
+}
+
 #ifdef UDE_PROFILE
 void ude_debug_set_prof(unsigned long long* p) { ude::g_prof_buffer = p; }
 #endif

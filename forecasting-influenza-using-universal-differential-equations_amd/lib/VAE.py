@@ -210,11 +210,13 @@ class VAE:
         self._pred_src = (y_pred, n_samples, B, None, None) if training else None
         return y_pred
 
-    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None):
+    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
-        ``quantiles``, and with targets ``y_true`` (B, T, R) the per-day Metrics nll / skill / mae).
+        ``quantiles``, and with targets ``y_true`` (B, T, R) the per-day Metrics nll / skill / mae;
+        ``verify`` -- True or an ``ude_amd.forecast.Verify`` -- adds the scores of the ensemble itself:
+        CRPS, weighted interval score, coverage, PIT, empirical multibin skill, per day and per region).
         The draw is ``__call__``'s: one ``torch.randn(n_samples, B, R, ld_enc)``, the same encoding
         and reparameterisation, under ``torch.no_grad()``.  On a HIP device with an eligible model the
         inference solve's decoder epilogue emits the prediction (no latent, no checkpoint) and the
@@ -243,12 +245,13 @@ class VAE:
                     self.latent = odeint(self.ode, z, t, method="rk4", options=dict(step_size=t[1] - t[0]))
                     yhat = self.dec(self.latent[..., :3]).reshape(len(t), n_samples * B, self.n_regions)
             return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler,
-                                                 quantiles=quantiles)
+                                                 quantiles=quantiles, verify=verify)
         y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
         if not self.uncertainty:
             n_samples = 1
         yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
-        return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles)
+        return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles,
+                                             verify=verify)
 
     def _fused_head(self, y_pred, y_true, losses):
         """(nll, reg, per-group prediction mean / std) for this model's latest training prediction:

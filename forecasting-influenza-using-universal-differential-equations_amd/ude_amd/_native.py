@@ -45,7 +45,7 @@ EXPORTED_SYMBOLS = ("ude_supported", "ude_query", "ude_pack_weights", "ude_pack_
                     "ude_rhs_eval_vjp", "ude_lincomb", "ude_scaled_sumsq", "ude_build_info",
                     "ude_rk4_forward_ex", "ude_rk4_forward_dec_ex", "ude_rk4_backward_ex", "ude_lincomb_hc",
                     "ude_dopri_ratio", "ude_rk4_forecast_dec", "ude_forecast_summary_workspace",
-                    "ude_forecast_summary")
+                    "ude_forecast_summary", "ude_forecast_verify_workspace", "ude_forecast_verify")
 SUMSQ_WS = 1025          # doubles of ude_scaled_sumsq's output / workspace (UDE_SUMSQ_WS)
 
 
@@ -198,6 +198,12 @@ class NativeLib:
         L.ude_forecast_summary_workspace.restype = i32
         L.ude_forecast_summary.argtypes = [i32s, i32s, i32s, i32s, vp, vp, vp, vp, i32s, vp, vp, vp, vp, vp, vp]
         L.ude_forecast_summary.restype = i32
+        L.ude_forecast_verify_workspace.argtypes = [i32s, i32s, i32s, i32s, i32s, i32s, i32s,
+                                                    ctypes.POINTER(ctypes.c_int64)]
+        L.ude_forecast_verify_workspace.restype = i32
+        L.ude_forecast_verify.argtypes = [i32s, i32s, i32s, i32s, vp, vp, vp, vp, i32s, vp, i32s, i32s, vp, vp, vp, vp,
+                                          vp, vp, vp, vp]
+        L.ude_forecast_verify.restype = i32
 
     def supported(self, desc: UdeModelDesc) -> bool:
         return bool(self.lib.ude_supported(ctypes.byref(desc)))
@@ -369,6 +375,18 @@ class NativeLib:
     def forecast_summary(self, T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, scores, stream) -> None:
         check(self.lib.ude_forecast_summary(int(T), int(S), int(B), int(R), yhat, scale, y_true, q, int(n_q), ws,
                                             mean, std, quant, scores, stream), "ude_forecast_summary")
+
+    def forecast_verify_workspace(self, T, S, B, R, n_q, n_alpha, n_pit) -> int:
+        out = ctypes.c_int64(0)
+        check(self.lib.ude_forecast_verify_workspace(int(T), int(S), int(B), int(R), int(n_q), int(n_alpha),
+                                                     int(n_pit), ctypes.byref(out)), "ude_forecast_verify_workspace")
+        return int(out.value)
+
+    def forecast_verify(self, T, S, B, R, yhat, scale, y_true, q, n_q, alpha, n_alpha, n_pit, ws, mean, std, quant,
+                        scores, day, region, stream) -> None:
+        check(self.lib.ude_forecast_verify(int(T), int(S), int(B), int(R), yhat, scale, y_true, q, int(n_q), alpha,
+                                           int(n_alpha), int(n_pit), ws, mean, std, quant, scores, day, region,
+                                           stream), "ude_forecast_verify")
 
     def build_info(self) -> str:
         return self.lib.ude_build_info().decode()

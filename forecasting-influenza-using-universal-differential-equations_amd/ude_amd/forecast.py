@@ -12,12 +12,17 @@ written.  ``ensemble_summary`` turns ``y_hat`` into a ``Forecast`` (mean, popula
 and against targets the per-day Metrics.nll / skill / mae) in one read of ``y_hat``
 (ude_forecast_summary; fp64 after the load, fixed-order sums: the same bits run to run).  On a CPU
 tensor the same definitions run on torch fp64 operators.
+
+``verify=`` adds scores of the ensemble itself, from the tile the summary kernel has sorted
+(ude_forecast_verify): CRPS, the weighted interval score, interval coverage, the PIT histogram and
+the empirical multibin skill (lib/Metrics.py ``mb_log(bins=True)``'s window on the samples), per day
+and per (day, region).
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, fields
-from typing import Optional, Sequence
+from typing import Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -28,6 +33,27 @@ from . import fused as _fused
 
 MASS_FLOOR = 4.5399929762484854e-05      # lib/Metrics.py mb_log: an exactly zero mass -> e^-10
 MAX_QUANTILE_SAMPLES = 1024              # FC_MAX_SQ (csrc/ude_forecast.h)
+FLUSIGHT_ALPHAS = (0.02, 0.05, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
+MAX_ALPHAS = 16                          # FC_MAX_ALPHA
+MAX_PIT_BINS = 64                        # FC_MAX_PIT
+
+
+@dataclass(frozen=True)
+class Verify:
+    """What ``verify=`` scores: the central intervals ``1 - alpha`` of the weighted interval score
+    and of ``coverage`` (each alpha in (0, 1), at most 16), and the number of PIT bins (at most 64)."""
+    alphas: Tuple[float, ...] = FLUSIGHT_ALPHAS
+    pit_bins: int = 10
+
+    def __post_init__(self):
+        alphas = tuple(float(a) for a in self.alphas)
+        object.__setattr__(self, "alphas", alphas)
+        if not 1 <= len(alphas) <= MAX_ALPHAS:
+            raise ValueError(f"Verify: {len(alphas)} alphas (1 to {MAX_ALPHAS})")
+        if not all(0.0 < a < 1.0 for a in alphas):
+            raise ValueError("Verify: every alpha must lie in (0, 1)")
+        if int(self.pit_bins) != self.pit_bins or not 1 <= self.pit_bins <= MAX_PIT_BINS:
+            raise ValueError(f"Verify: pit_bins {self.pit_bins} (1 to {MAX_PIT_BINS})")
 
 
 @dataclass
@@ -35,13 +61,33 @@ class Forecast:
     """Per-(window, day, region) summary of an ensemble forecast (fp64 tensors on the forecast's
     device): ``mean`` / ``std`` (B, T, R) (population std, as numpy.std), ``quantiles`` (Q, B, T, R)
     or None, and -- when targets were given -- ``nll`` / ``skill`` / ``mae`` (T,): lib/Metrics.py's
-    scores of every time index over its B * R groups."""
+    scores of every time index over its B * R groups.
+
+    With ``verify`` (K alphas, J PIT bins), scores of the ensemble itself: ``crps`` / ``wis`` (T,)
+    (means over the B * R groups), ``ens_skill`` (T,) = exp(mean log empirical mass of the multibin
+    window, an empty window counting as MASS_FLOOR), ``coverage`` (K, T) (fraction of groups whose
+    central 1 - alpha_k interval holds the target), ``pit`` (T, J) (fraction of groups per bin of the
+    target's mid-rank; rows sum to 1), and the per-region forms (means over the B windows)
+    ``nll_r`` / ``skill_r`` / ``mae_r`` / ``crps_r`` / ``wis_r`` / ``ens_skill_r`` (T, R) and
+    ``coverage_r`` (K, T, R)."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
     nll: Optional[torch.Tensor] = None
     skill: Optional[torch.Tensor] = None
     mae: Optional[torch.Tensor] = None
+    crps: Optional[torch.Tensor] = None
+    wis: Optional[torch.Tensor] = None
+    ens_skill: Optional[torch.Tensor] = None
+    coverage: Optional[torch.Tensor] = None
+    pit: Optional[torch.Tensor] = None
+    nll_r: Optional[torch.Tensor] = None
+    skill_r: Optional[torch.Tensor] = None
+    mae_r: Optional[torch.Tensor] = None
+    crps_r: Optional[torch.Tensor] = None
+    wis_r: Optional[torch.Tensor] = None
+    ens_skill_r: Optional[torch.Tensor] = None
+    coverage_r: Optional[torch.Tensor] = None
 
     def _map(self, fn):
         return Forecast(**{f.name: (None if getattr(self, f.name) is None else fn(getattr(self, f.name)))
@@ -82,10 +128,59 @@ def _scale_vector(scale, R: int, device) -> Optional[torch.Tensor]:
 
 
 def _ndtr(x: torch.Tensor) -> torch.Tensor:
-    return torch.special.ndtr(x)
+    """scipy.special.ndtr's branches (cephes ndtr.c), as the kernel's fc_ndtr.  torch.special.ndtr forms
+    (1 + erf) / 2 in the upper tail, which rounds twice: a mass of 1e-9 six standard deviations above the
+    mean then differs from SciPy's in its seventh digit."""
+    a = x * 0.70710678118654752440
+    z = a.abs()
+    half = 0.5 * torch.erfc(z)
+    return torch.where(z < 0.70710678118654752440, 0.5 + 0.5 * torch.erf(a), torch.where(a > 0, 1.0 - half, half))
 
 
-def _summary_torch(yhat, S, B, y_true, scale, q) -> Forecast:
+def _lerp_quantile(vs: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
+    """numpy.quantile 'linear' (_lerp) of ``vs`` (T, S, B, R), sorted along dim 1, at the levels ``q``
+    (Q,): (Q, T, B, R).  The arithmetic of the kernel's fc_quantile."""
+    S = vs.shape[1]
+    h = (S - 1) * q
+    lo = h.floor().clamp(0, S - 1)
+    gm = (h - lo).view(-1, 1, 1, 1)
+    lo = lo.long()
+    hi = (lo + 1).clamp(max=S - 1)
+    x, y = vs[:, lo].movedim(1, 0), vs[:, hi].movedim(1, 0)
+    d = y - x
+    return torch.where(gm >= 0.5, y - d * (1.0 - gm), x + d * gm)
+
+
+def _verify_torch(out: Forecast, v, y, mean, nll, mass, verify: Verify) -> None:
+    """The ``verify`` fields from v (T, S, B, R) and y / mean / nll / mass (T, B, R), all scaled fp64."""
+    T, S, B, R = v.shape
+    n = float(B * R)
+    vs = v.sort(dim=1).values
+    rank = torch.arange(S, dtype=torch.float64, device=v.device) * 2 - (S - 1)
+    crps = (v - y.unsqueeze(1)).abs().sum(1) / S - (rank.view(1, S, 1, 1) * vs).sum(1) / (S * S)
+    al = torch.tensor(verify.alphas, dtype=torch.float64, device=v.device)
+    K, J = al.numel(), int(verify.pit_bins)
+    lo, up = _lerp_quantile(vs, 0.5 * al), _lerp_quantile(vs, 1.0 - 0.5 * al)          # (K, T, B, R)
+    med = _lerp_quantile(vs, torch.tensor([0.5], dtype=torch.float64, device=v.device))[0]
+    a4 = al.view(K, 1, 1, 1)
+    wis = (0.5 * (y - med).abs() + (0.5 * a4 * ((up - lo) + (2.0 / a4) * (lo - y).clamp(min=0)
+                                                + (2.0 / a4) * (y - up).clamp(min=0))).sum(0)) / (K + 0.5)
+    cover = ((lo <= y) & (y <= up)).to(torch.float64)
+    mid = (v < y.unsqueeze(1)).sum(1) + (v <= y.unsqueeze(1)).sum(1)                   # n_lt + n_le
+    pit_bin = torch.div(J * mid, 2 * S, rounding_mode="floor").clamp(max=J - 1)
+    cb = (y * 10.0).floor() / 10.0
+    n_win = ((v >= (cb - 0.5).unsqueeze(1)) & (v < (cb + 0.6).unsqueeze(1))).sum(1)
+    emp = torch.where(n_win == 0, torch.full_like(y, MASS_FLOOR), n_win.to(torch.float64) / S)
+    out.crps, out.wis = crps.mean((1, 2)), wis.mean((1, 2))
+    out.ens_skill = emp.log().mean((1, 2)).exp()
+    out.coverage = cover.sum((2, 3)) / n
+    out.pit = torch.nn.functional.one_hot(pit_bin, J).to(torch.float64).sum((1, 2)) / n
+    out.nll_r, out.skill_r, out.mae_r = nll.mean(1), mass.log().mean(1).exp(), (y - mean).abs().mean(1)
+    out.crps_r, out.wis_r, out.ens_skill_r = crps.mean(1), wis.mean(1), emp.log().mean(1).exp()
+    out.coverage_r = cover.sum(2) / float(B)
+
+
+def _summary_torch(yhat, S, B, y_true, scale, q, verify: Optional[Verify] = None) -> Forecast:
     T, N, R = yhat.shape
     v = yhat.detach().to(torch.float64).reshape(T, S, B, R)
     if scale is not None:
@@ -106,6 +201,8 @@ def _summary_torch(yhat, S, B, y_true, scale, q) -> Forecast:
         out.nll = nll.mean((1, 2))
         out.skill = mass.log().mean((1, 2)).exp()
         out.mae = (y - mean).abs().mean((1, 2))
+        if verify is not None:
+            _verify_torch(out, v, y, mean, nll, mass, verify)
     return out
 
 
@@ -120,18 +217,29 @@ def _library() -> Optional["_native.NativeLib"]:
 
 
 def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Optional[torch.Tensor] = None,
-                     scale=None, quantiles: Optional[Sequence[float]] = None) -> Forecast:
+                     scale=None, quantiles: Optional[Sequence[float]] = None, verify=None) -> Forecast:
     """Summary of ``yhat`` (T, S*B, R) (sample n = s*B + b, as the solve emits it) over its S
     samples: see ``Forecast``.  ``scale``: per-region multiplier of predictions and targets (the
     data scaler); ``y_true`` (B, T, R); ``quantiles``: levels in [0, 1] (numpy.quantile, 'linear').
-    A HIP tensor runs ude_forecast_summary; a CPU tensor (or no library) the same definitions in
-    torch fp64."""
+    ``verify``: None, True (``Verify()``) or a ``Verify`` -- with targets, also the scores of the
+    ensemble itself (``Forecast``); the other fields keep their bits.  A HIP tensor runs
+    ude_forecast_summary (ude_forecast_verify with ``verify``, n_samples <= 1024); a CPU tensor (or no
+    library) the same definitions in torch fp64."""
     if yhat.dim() != 3 or yhat.shape[1] != n_samples * batch:
         raise ValueError(f"ensemble_summary: y_hat {tuple(yhat.shape)} is not (T, {n_samples}*{batch}, R)")
     T, N, R = (int(v) for v in yhat.shape)
     S, B = int(n_samples), int(batch)
     if y_true is not None and tuple(y_true.shape) != (B, T, R):
         raise ValueError(f"ensemble_summary: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
+    if verify is True:
+        verify = Verify()
+    if verify is not None:
+        if not isinstance(verify, Verify):
+            raise TypeError("ensemble_summary: verify is None, True or a Verify")
+        if y_true is None:
+            raise ValueError("ensemble_summary: verify needs the targets y_true")
+        if S > MAX_QUANTILE_SAMPLES and yhat.is_cuda:
+            raise ValueError(f"ensemble_summary: verify needs n_samples <= {MAX_QUANTILE_SAMPLES}")
     dev = yhat.device
     sc = _scale_vector(scale, R, dev)
     q = None
@@ -143,7 +251,7 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
             raise ValueError(f"ensemble_summary: quantiles need n_samples <= {MAX_QUANTILE_SAMPLES}")
     lib = _library() if yhat.is_cuda else None
     if lib is None:
-        return _summary_torch(yhat, S, B, y_true, sc, q)
+        return _summary_torch(yhat, S, B, y_true, sc, q, verify)
     n_q = 0 if q is None else int(q.numel())
     yh = yhat.detach().to(torch.float32).contiguous()
     yt = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
@@ -153,14 +261,31 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
         std = torch.empty((B, T, R), **f64)
         quant = torch.empty((n_q, B, T, R), **f64) if n_q else None
         scores = torch.empty((3, T), **f64) if yt is not None else None
-        ws = torch.empty(max(lib.forecast_summary_workspace(T, S, B, R, n_q) // 8, 1), **f64) if yt is not None else None
         p = _fused._ptr
-        with _fused._timed("forecast_summary"):
-            lib.forecast_summary(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, p(ws), mean.data_ptr(),
-                                 std.data_ptr(), p(quant), p(scores), _fused._stream(dev))
+        if verify is None:
+            ws = torch.empty(max(lib.forecast_summary_workspace(T, S, B, R, n_q) // 8, 1), **f64) if yt is not None else None
+            with _fused._timed("forecast_summary"):
+                lib.forecast_summary(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, p(ws), mean.data_ptr(),
+                                     std.data_ptr(), p(quant), p(scores), _fused._stream(dev))
+        else:
+            K, J = len(verify.alphas), int(verify.pit_bins)
+            al = torch.tensor(verify.alphas, **f64)
+            day = torch.empty((3 + K + J, T), **f64)
+            region = torch.empty((6 + K, T, R), **f64)
+            ws = torch.empty(lib.forecast_verify_workspace(T, S, B, R, n_q, K, J) // 8, **f64)
+            with _fused._timed("forecast_verify"):
+                lib.forecast_verify(T, S, B, R, yh.data_ptr(), p(sc), p(yt), p(q), n_q, al.data_ptr(), K, J,
+                                    ws.data_ptr(), mean.data_ptr(), std.data_ptr(), p(quant), scores.data_ptr(),
+                                    day.data_ptr(), region.data_ptr(), _fused._stream(dev))
     out = Forecast(mean, std, quant)
     if scores is not None:
         out.nll, out.skill, out.mae = scores[0], scores[1].exp(), scores[2]
+    if verify is not None:
+        out.crps, out.wis, out.ens_skill = day[0], day[1], day[2].exp()
+        out.coverage, out.pit = day[3:3 + K], day[3 + K:].t().contiguous()
+        out.nll_r, out.skill_r, out.mae_r = region[0], region[1].exp(), region[2]
+        out.crps_r, out.wis_r, out.ens_skill_r = region[3], region[4], region[5].exp()
+        out.coverage_r = region[6:]
     return out
 
 

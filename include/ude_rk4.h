@@ -383,6 +383,27 @@ int ude_forecast_summary(int32_t T, int32_t S, int32_t B, int32_t R, const float
                          const float* y_true, const double* q, int32_t n_q, void* ws, double* mean, double* std,
                          double* quant, double* scores, ude_stream_t stream);
 
+/* ude_forecast_verify: ude_forecast_summary (same arguments, the same bits in mean / std / quant / scores;
+ * y_true required, S <= 1024 always: the tile is always sorted) plus scores of the ensemble itself.  With
+ * x_(0) <= .. <= x_(S-1) the sorted v of a group, K = n_alpha levels alpha[k] in (0, 1) (1 <= K <= 16,
+ * not checked: device memory), l_k / u_k / m the 'linear' quantiles at alpha_k / 2, 1 - alpha_k / 2, 0.5 and
+ * J = n_pit bins (1 <= J <= 64), per group
+ *   crps  = sum_i |v_i - y| / S - sum_i (2 i - S + 1) x_(i) / S^2
+ *   wis   = (|y - m| / 2 + sum_k alpha_k / 2 [(u_k - l_k) + 2 / alpha_k ((l_k - y)+ + (y - u_k)+)]) / (K + 1/2)
+ *   cov_k = [l_k <= y <= u_k],   pit bin = min(J - 1, J (#{v < y} + #{v <= y}) div 2 S)
+ *   mass  = #{c - 0.5 <= v < c + 0.6} / S with c = floor(10 y) / 10, an empty window -> 4.5399929762484854e-05
+ * (lib/Metrics.py mb_log(bins=True)'s window on the samples).  day (3 + K + J, T): per time index the mean
+ * over its B*R groups of [crps, wis, log mass, cov_0 .. cov_{K-1}] and the fraction of groups in each PIT
+ * bin.  region (6 + K, T, R): the mean over the B windows of a (t, r) of [the three terms of scores, crps, wis,
+ * log mass, cov_k].  Counts are summed exactly and divided once.  Fixed-order sums, no atomics: the same
+ * bits run to run.  ws: ude_forecast_verify_workspace() bytes. */
+int ude_forecast_verify_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int32_t n_alpha,
+                                  int32_t n_pit, int64_t* ws_bytes);
+int ude_forecast_verify(int32_t T, int32_t S, int32_t B, int32_t R, const float* yhat, const double* scale,
+                        const float* y_true, const double* q, int32_t n_q, const double* alpha, int32_t n_alpha,
+                        int32_t n_pit, void* ws, double* mean, double* std, double* quant, double* scores,
+                        double* day, double* region, ude_stream_t stream);
+
 /* Library build tag (for logs / tests). */
 const char* ude_build_info(void);
 

@@ -7,7 +7,11 @@ runs each, wall clock between device synchronisations:
 
   (a) host: model(x, t, 128, training=False) -> host copy -> NumPy mean / std -> Metrics.nll / skill
       at the four horizons (lib/utils.py:21-26, :53-54);
-  (b) fused: model.forecast(x, t, 128, y_true, scaler).cpu().
+  (b) fused: model.forecast(x, t, 128, y_true, scaler).cpu();
+  (c) fused + quantiles: (b) with quantiles=[0.025, 0.5, 0.975] -- the summary kernel sorts its tile;
+  (d) fused + verify: (b) with verify=True -- the ensemble's own scores from the sorted tile
+      (ude_forecast_verify in place of ude_forecast_summary).  (b), (c) and (d) alternate run by run,
+      so their summary times come from the same minutes of the device.
 
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
@@ -42,10 +46,18 @@ def stats(xs):
 
 
 def timed(fn, runs, warmup):
+    return timed_alternating([fn], runs, warmup)[0]
+
+
+def timed_alternating(fns, runs, warmup):
+    """One result per function; the functions take turns, run by run."""
     for _ in range(warmup):
-        fn()
-    wall, span, kern = [], [], []
-    for _ in range(runs):
+        for fn in fns:
+            fn()
+    acc = [([], [], []) for _ in fns]
+    for i in range(runs * len(fns)):
+        fn = fns[i % len(fns)]
+        wall, span, kern = acc[i % len(fns)]
         fused.EVENTS = []
         e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
         torch.cuda.synchronize()
@@ -60,8 +72,8 @@ def timed(fn, runs, warmup):
             per[kind] = per.get(kind, 0.0) + a.elapsed_time(b)
         kern.append(per)
         fused.EVENTS = None
-    native = {kind: stats([k[kind] for k in kern]) for kind in kern[0]}
-    return {"wall_ms": stats(wall), "device_span_ms": stats(span), "native_calls_ms": native}
+    return [{"wall_ms": stats(wall), "device_span_ms": stats(span),
+             "native_calls_ms": {kind: stats([k[kind] for k in kern]) for kind in kern[0]}} for wall, span, kern in acc]
 
 
 def main():
@@ -94,11 +106,15 @@ def main():
         return [(Metrics.nll(y_te[:, g, :], mu[:, g, :], sd[:, g, :]),
                  Metrics.skill(y_te[:, g, :], mu[:, g, :], sd[:, g, :])) for g in horizons]
 
-    def fusedf(e1=None):
-        fc = model.forecast(x, t, n_samples=S, y_true=y_test, scaler=scaler).cpu()
-        if e1 is not None:
-            e1.record()
-        return [(float(fc.nll[g]), float(fc.skill[g])) for g in horizons]
+    def fused_with(**kw):
+        def run(e1=None):
+            fc = model.forecast(x, t, n_samples=S, y_true=y_test, scaler=scaler, **kw).cpu()
+            if e1 is not None:
+                e1.record()
+            return [(float(fc.nll[g]), float(fc.skill[g])) for g in horizons]
+        return run
+
+    fusedf = fused_with()
 
     torch.manual_seed(7)
     ra = host()
@@ -106,7 +122,11 @@ def main():
     rb = fusedf()
     agree = max(abs(p - q) / max(abs(q), 1e-30) for u, v in zip(rb, ra) for p, q in zip(u, v))
     res_a = timed(host, a.runs, a.warmup)
-    res_b = timed(fusedf, a.runs, a.warmup)
+    res_b, res_c, res_d = timed_alternating([fusedf, fused_with(quantiles=[0.025, 0.5, 0.975]),
+                                             fused_with(verify=True)], a.runs, a.warmup)
+    from ude_amd import _native
+    ws = {"summary": _native.prebuilt().forecast_summary_workspace(57, S, B, R, 0),
+          "verify": _native.prebuilt().forecast_verify_workspace(57, S, B, R, 0, 11, 10)}
     try:
         commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True,
                                 text=True).stdout.strip() or None
@@ -116,6 +136,7 @@ def main():
            "shape": {"R": R, "L": 8, "S": S, "B": B, "N": S * B, "T": 57},
            "latent_path_used_by_forecast": model.latent is not None,
            "scores_rel_diff_fused_vs_host": agree, "host": res_a, "fused": res_b,
+           "fused_quantiles": res_c, "fused_verify": res_d, "workspace_bytes": ws,
            "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}
     print(json.dumps(out))
 
