@@ -70,21 +70,30 @@ struct Ops {
   static_assert(!M::HOIST || DY0_STATIC_LDS <= 160 * 1024, "dy0 static time sums do not fit the 160 KiB LDS");
 
   // ---- the forward kernel's variants ---------------------------------------------------------------
-  // One row per ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES> this model has:
+  // One row per ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN> this model has:
   //   train: stores the training checkpoint;  dec: the decoder epilogue (y_hat, no latent);
   //   split: the 8-wave kernel (Model::SPLIT_FWD);  res: resident weights, one workgroup per CU
-  //   (Model::FWD_RES).
+  //   (Model::FWD_RES);  dyn: the dynamics channels beside y_hat (inference dec, deterministic weights).
   // fwd_variant calls f(kernel, threads, dynamic LDS bytes) for the row of the given facts and returns
   // f's result, or NO_VARIANT when the model has no such kernel.  Inference with the decoder epilogue
   // (the forecast) stores nothing, so the Recompute view has none.
   static constexpr int NO_VARIANT = 1;
-  template <bool TRAIN, bool DEC, bool SPLIT, bool RES, class F>
+  template <bool TRAIN, bool DEC, bool SPLIT, bool RES, bool DYN = false, class F>
   static int fwd_row(F&& f) {
-    return f((const void*)&ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES>, SPLIT ? 2 * NTHREADS : NTHREADS,
+    return f((const void*)&ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN>, SPLIT ? 2 * NTHREADS : NTHREADS,
              DEC ? M::LDS_F_DEC : M::LDS_F);
   }
   template <class F>
-  static int fwd_variant(bool train, bool dec, bool split, bool res, F&& f) {
+  static int fwd_variant(bool train, bool dec, bool split, bool res, bool dyn, F&& f) {
+    if (dyn) {
+      if constexpr (!is_recompute<M>::value && !M::BAYES) {
+        if (!train && dec && !split && !res) return fwd_row<false, true, false, false, true>(f);
+        if constexpr (M::FWD_RES) {
+          if (!train && dec && !split && res) return fwd_row<false, true, false, true, true>(f);
+        }
+      }
+      return NO_VARIANT;
+    }
     const auto is = [=](bool t, bool d, bool s, bool r) { return train == t && dec == d && split == s && res == r; };
     if (is(1, 0, 0, 0)) return fwd_row<true, false, false, false>(f);
     if (is(0, 0, 0, 0)) return fwd_row<false, false, false, false>(f);
@@ -111,8 +120,8 @@ struct Ops {
     static bool done = false;
     if (done) return UDE_OK;
     // record + (when it fits) the schedule: up to the full 160 KiB, for every forward variant there is
-    for (int v = 0; v < 16; ++v) {
-      const int rc = fwd_variant(v & 1, v & 2, v & 4, v & 8, [](const void* k, int, int) -> int {
+    for (int v = 0; v < 32; ++v) {
+      const int rc = fwd_variant(v & 1, v & 2, v & 4, v & 8, v & 16, [](const void* k, int, int) -> int {
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
         return UDE_OK;
       });
@@ -141,7 +150,7 @@ struct Ops {
   static int grid_fwd(int device, int n_tiles, int* gf, int* cus = nullptr) {
     int rc = ensure_attrs();
     if (rc) return rc;
-    return fwd_variant(true, false, false, false, [&](const void* k, int threads, int lds) {
+    return fwd_variant(true, false, false, false, false, [&](const void* k, int threads, int lds) {
       return occupancy_grid(k, threads, lds, device, n_tiles, gf, cus);
     });
   }
@@ -316,6 +325,24 @@ struct Ops {
     }
   }
 
+  // The forecast with the dynamics channels: forecast_dec's outputs (the same bits) plus dyn (C, T, N, R),
+  // C = dyn_channels<M>(): S, I, R[, beta, gamma, r_eff][, Fa] at every output time.  Deterministic weights
+  // only: a Bayesian solve has no weight sample for the evaluation at its last output time.
+  static int forecast_dyn(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
+                          const float* dec_pack, float* yhat, float* dyn, double* stats_slab,
+                          const UdeSideStats* st, unsigned* ctl, hipStream_t s) {
+    if constexpr (is_recompute<M>::value || M::BAYES) {
+      return UDE_E_UNSUPPORTED;
+    } else {
+    if (!pack || !sched || !y0 || !dec_pack || !yhat || !dyn || !stats_slab || !stats_ok(st)) return UDE_E_INVALID;
+    if (p->n_steps < 1) return UDE_E_INVALID;
+    KArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dec_pack = dec_pack; a.yhat = yhat; a.dyn = dyn;
+    return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
+    }
+  }
+
   // Backward of the decoder epilogue: dl3 (T, N, R, 3) for ude_rk4_backward_sir, d W_dec, d b_dec.
   static int dec_backward(const UdeProblem* p, const void* sched, const float* ckpt, const float* dyhat,
                           const float* W, const float* grad_reg, void* ws, float* dl3, float* dW, float* db,
@@ -462,9 +489,10 @@ struct Ops {
     return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
   }
 
-  // The one forward launch behind forward / forward_dec / forecast_dec.  `a` arrives zeroed except for
-  // what only its entry has (outputs, checkpoint, decoder pack); a.ckpt says whether the solve stores
-  // the training checkpoint, a.yhat whether it runs the decoder epilogue.  Kernel selection:
+  // The one forward launch behind forward / forward_dec / forecast_dec / forecast_dyn.  `a` arrives zeroed
+  // except for what only its entry has (outputs, checkpoint, decoder pack); a.ckpt says whether the solve
+  // stores the training checkpoint, a.yhat whether it runs the decoder epilogue, a.dyn whether it emits the
+  // dynamics channels.  Kernel selection:
   //   split    iff it stores a checkpoint, the model has the 8-wave kernel and every tile has a CU of
   //            its own (so an inference solve, the forecast included, never splits);
   //   resident else iff fwd_res(): one workgroup per CU, gf = min(n_tiles, cus) (<= the slabs' size);
@@ -488,7 +516,7 @@ struct Ops {
     const bool split = train && M::SPLIT_FWD && n_tiles <= cus;
     const bool res = !split && fwd_res(n_tiles, cus);
     if (res) gf = n_tiles < cus ? n_tiles : cus;
-    rc = fwd_variant(train, dec, split, res, [&](const void* k, int threads, int lds) -> int {
+    rc = fwd_variant(train, dec, split, res, a.dyn != nullptr, [&](const void* k, int threads, int lds) -> int {
       void* args[] = {&a};
       HIPCHK(hipLaunchKernel(k, dim3(gf), dim3(threads), args, lds, s));
       return UDE_OK;
@@ -929,6 +957,8 @@ struct Entry {
                       float*, hipStream_t);
   int (*forecast_dec)(const UdeProblem*, const float*, const void*, const float*, const float*, float*, double*,
                       double*, const UdeSideStats*, unsigned*, float*, hipStream_t);
+  int (*forecast_dyn)(const UdeProblem*, const float*, const void*, const float*, const float*, float*, float*,
+                      double*, const UdeSideStats*, unsigned*, hipStream_t);
 };
 
 template <class M>
@@ -938,7 +968,7 @@ constexpr Entry make_entry() {
                &LossOps<M>::backward, &LossOps<M>::backward_sir, &EvalOps<M>::workspace, &EvalOps<M>::forward,
                &EvalOps<M>::vjp, &Ops<M>::dec_pack, &Ops<M>::forward_dec, &Ops<M>::dec_backward,
                &Ops<M>::nll_workspace, &Ops<M>::nll_forward, &Ops<M>::nll_backward, &EvalOps<M>::fused,
-               &Ops<M>::forecast_dec};
+               &Ops<M>::forecast_dec, &Ops<M>::forecast_dyn};
 }
 
 

@@ -98,7 +98,13 @@ struct KArgs {
   double* o_sums;             // 5 doubles: sum beta, sum gamma, sum beta^2, sum gamma^2, sum Fa^2 (nullable)
   float* o_reg;               // DEC: latent_init_loss (1 float)
   double n_eval;              // 4 n_steps N R: the number of recorded rates per statistic
+  float* dyn;                 // DYN forward: (C, T, N, R) dynamics channels (dyn_channels<M>() of them)
 };
+
+// The channels of the DYN forward, in order: s, i, r; beta, gamma, r_eff (rate net); fa_s, fa_i, fa_r
+// (augmentation net).  Channel c of output time j is the (N, R) block at ((c * T + j) * N) * R.
+template <class M>
+constexpr int dyn_channels() { return 3 + (M::HAS_P ? 3 : 0) + (M::HAS_A ? 3 : 0); }
 
 // latent_init_loss summand (lib/train_functions.py:116-126): |x| where x < 0, |1 - x| where x > 1
 __device__ __forceinline__ float reg_term(float v) {
@@ -808,8 +814,17 @@ __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
 // outnumber the CUs): one workgroup per CU with every forward fragment resident in VGPRs for the whole
 // launch -- no phase waits on the L2 latency of its weights (the few-tile / strong-scaling shard case,
 // where no second workgroup on the CU hides it).
-template <class M, bool TRAIN, int W, bool SPLIT = false, bool DEC = false, bool RES = false>
+// DYN (the inference DEC forward, deterministic weights): beside y_hat, every output time emits the
+// dynamics channels of dyn_channels<M>() into A.dyn (C, T, N, R): the state S, I, R and the nets' outputs
+// evaluated at that state -- beta, gamma (unmasked, as the reference appends them to `params`),
+// r_eff = beta S / gamma, and the raw Fa (before Fa_w and the mask, as appended to `tracker`).  An output
+// time that starts a step takes them from that step's stage 0, ahead of its flux pass (dyn_pass); the
+// last output time ends the last step and has no evaluation of the solve, so one more mlp_forward runs
+// on the final state and the same pass follows it: no RK update, no store but A.dyn, nothing added to
+// the side statistics.
+template <class M, bool TRAIN, int W, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false>
 __device__ void fwd_body(const KArgs& A, float* lds) {
+  static_assert(!DYN || (DEC && !TRAIN && !SPLIT && !M::BAYES), "DYN: the deterministic inference DEC forward only");
   constexpr int SR = M::SR_F;
   constexpr int SL = M::SLOTS;
   int tid = threadIdx.x;
@@ -873,6 +888,47 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             }
           }
         });
+      }
+    };
+
+    // DYN: the channels of output jo, from the record of a finished mlp_forward whose Y slot still holds
+    // the evaluated state.  A pass of its own over the thread's (trajectory, region) pairs, run between the
+    // layers' last barrier and the flux pass, when nothing of the flux pass is live: each thread reads and
+    // the flux pass then rewrites only its own pairs' Y slots, so no barrier separates the two.  Not a hot
+    // path (one stage in four, nine stores per pair): a rolled loop whose thread-derived addresses are
+    // formed here per use, not hoisted into registers the stage loop needs (at R = 49 the plain kernel is
+    // close to its 256 VGPRs).  4-B stores at stride R across the tile's trajectories, as the latent
+    // stores of the models without 16-B rows.
+    auto dyn_pass = [&](int jo) {
+      if constexpr (DYN) {
+        int td = threadIdx.x;
+        asm volatile("" : "+v"(td));
+        const size_t NR = (size_t)A.n_traj * M::R, CS = (size_t)(A.n_out + 1) * NR;
+        #pragma unroll 1
+        for (int p = td; p < M::PAIRS; p += NTHREADS) {
+          const int r = p / TT, t = p - r * TT;
+          const int n = n0 + t;
+          if (n < A.n_traj) {
+            const float* rec = lds + t * SR;
+            float* dst = A.dyn + (size_t)jo * NR + (size_t)n * M::R + r;
+            const float s = rec[M::Y_OFF + 3 * r];
+            dst[0] = s;
+            dst[CS] = rec[M::Y_OFF + 3 * r + 1];
+            dst[2 * CS] = rec[M::Y_OFF + 3 * r + 2];
+            if constexpr (M::HAS_P) {
+              const float b = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r]);
+              const float gm = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1]);
+              dst[3 * CS] = b;
+              dst[4 * CS] = gm;
+              dst[5 * CS] = (b * s) / gm;
+            }
+            if constexpr (M::HAS_A) {
+              constexpr int c0 = M::HAS_P ? 6 : 3;
+#pragma unroll
+              for (int c = 0; c < 3; ++c) dst[(c0 + c) * CS] = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
+            }
+          }
+        }
       }
     };
 
@@ -948,6 +1004,13 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
       // checkpoint / activation store in flight)
       if constexpr (DEC) asm volatile("" : "+v"(tid));
       const float dt = sc.dt[step];
+      // DYN: the output time this step starts on (0 = y0, or the grid-hit output that ended the previous
+      // step), -1 when it starts between outputs
+      int dyn_jo = -1;
+      if constexpr (DYN) {
+        if (step == 0) dyn_jo = 0;
+        else if (sc.out_start[step - 1] < sc.out_start[step]) dyn_jo = sc.out_j[sc.out_start[step - 1]];
+      }
       for (int j = 0; j < 4; ++j) {
         // BAYES: evaluation 4 step + j has its own weight sample
         Rsrc rse = rs;
@@ -989,6 +1052,9 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
           }
         }
         UDE_STAMP(pf, 0);
+        if constexpr (DYN) {
+          if (j == 0 && dyn_jo >= 0) dyn_pass(dyn_jo);
+        }
         if constexpr (UDE_ABL != 12) sfor<SL>([&](auto ss) {
           constexpr int sl = decltype(ss)::value;
           const int p = tid + sl * NTHREADS;
@@ -1119,6 +1185,19 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
         if (sc.out_start[step] < sc.out_start[step + 1]) dec_emit(sc.out_j[sc.out_start[step]]);
       }
     }
+    if constexpr (DYN) {
+      // the last output time: the nets at the final state.  The Y slot is only read (dec_emit of that
+      // output may still be reading it); the barrier at the end keeps the next tile's start (static
+      // features over the activation rows, the Y slot) behind this pass's reads.  The condition is the
+      // schedule's: uniform over the workgroup.
+      const int last = A.n_steps - 1;
+      if (sc.out_start[last] < sc.out_start[last + 1]) {
+        const int jo = sc.out_j[sc.out_start[last]];
+        mlp_forward<M, W, SR>(rs, lds, c1, lane, wr, pf);
+        dyn_pass(jo);
+        lds_sync();
+      }
+    }
   }
 
   // deterministic per-workgroup partial sums
@@ -1191,17 +1270,18 @@ __device__ void fwd_sbody(const KArgs& A, float* lds) {
 
 // SPLIT (training, Model::split_fwd, launched when every tile has a CU of its own): 8 waves.
 // DEC: the decoder epilogue (y_hat and latent_init_loss, no latent).
-template <class M, bool TRAIN, bool SPLIT = false, bool DEC = false, bool RES = false>
+// DYN: the dynamics channels beside y_hat (the deterministic inference DEC forward only; see fwd_body).
+template <class M, bool TRAIN, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false>
 __global__ __launch_bounds__(SPLIT ? 2 * NTHREADS : NTHREADS, (SPLIT || RES) ? 1 : 2) void ude_fwd_kernel(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (SPLIT) {
     if (w >= WAVES) { fwd_sbody<M, DEC>(a, lds); return; }
   }
-  if (w == 0) fwd_body<M, TRAIN, 0, SPLIT, DEC, RES>(a, lds);
-  else if (w == 1) fwd_body<M, TRAIN, 1, SPLIT, DEC, RES>(a, lds);
-  else if (w == 2) fwd_body<M, TRAIN, 2, SPLIT, DEC, RES>(a, lds);
-  else fwd_body<M, TRAIN, 3, SPLIT, DEC, RES>(a, lds);
+  if (w == 0) fwd_body<M, TRAIN, 0, SPLIT, DEC, RES, DYN>(a, lds);
+  else if (w == 1) fwd_body<M, TRAIN, 1, SPLIT, DEC, RES, DYN>(a, lds);
+  else if (w == 2) fwd_body<M, TRAIN, 2, SPLIT, DEC, RES, DYN>(a, lds);
+  else fwd_body<M, TRAIN, 3, SPLIT, DEC, RES, DYN>(a, lds);
 }
 
 // ============================================================================

@@ -210,7 +210,7 @@ class VAE:
         self._pred_src = (y_pred, n_samples, B, None, None) if training else None
         return y_pred
 
-    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None):
+    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
@@ -221,7 +221,16 @@ class VAE:
         and reparameterisation, under ``torch.no_grad()``.  On a HIP device with an eligible model the
         inference solve's decoder epilogue emits the prediction (no latent, no checkpoint) and the
         summary kernels read it once: nothing but the summary is copied to the host, and
-        ``self.latent`` is None afterwards.  Otherwise ``__call__(training=False)`` is summarised."""
+        ``self.latent`` is None afterwards.  Otherwise ``__call__(training=False)`` is summarised.
+
+        ``dynamics=True`` also fills ``Forecast.dynamics`` (``ude_amd.forecast.Dynamics``): per (window,
+        day, region) mean / std / ``quantiles`` over the same ensemble of the learned dynamics -- S, I,
+        R, the rate net's beta and gamma at each output state, R_eff = beta S / gamma and the
+        augmentation flux Fa.  On the fused path the same solve emits them beside the prediction
+        (ude_rk4_forecast_dyn; still no latent); a CPU model, a Bayesian RHS (evaluated at its mean
+        weights), output times between grid points or an RHS without a kernel take them from the
+        written latent instead (``ude_amd.forecast.latent_dynamics``), without touching
+        ``ode.params`` / ``ode.tracker``.  With ``dynamics=False`` nothing changes."""
         B = x.shape[0]
         dev_is_hip = torch.device(self.device).type == "cuda"
         lin = decoder_head.decoder_linear(self.dec)
@@ -238,20 +247,36 @@ class VAE:
                     n_samples = 1
                     self.mean = self.enc(x)
                     z = (models.reparam(eps, None, self.mean, n_samples, B, uncertainty=False) + 1e-5).unsqueeze(1)
-                yhat = ude_forecast.solve_decode_forecast(self.ode, z, t, t[1] - t[0], lin)
+                dyn = None
+                if dynamics:
+                    res = ude_forecast.solve_decode_dynamics(self.ode, z, t, t[1] - t[0], lin)
+                    yhat = None
+                    if res is not None:
+                        yhat, dyn = res[0], res[1:]
+                else:
+                    yhat = ude_forecast.solve_decode_forecast(self.ode, z, t, t[1] - t[0], lin)
                 if yhat is None:
-                    # not eligible (output times between grid points, an RHS without a kernel): the
-                    # latent path on the same draw
+                    # not eligible (output times between grid points, an RHS without a kernel; with
+                    # dynamics also a Bayesian RHS): the latent path on the same draw
                     self.latent = odeint(self.ode, z, t, method="rk4", options=dict(step_size=t[1] - t[0]))
                     yhat = self.dec(self.latent[..., :3]).reshape(len(t), n_samples * B, self.n_regions)
-            return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler,
-                                                 quantiles=quantiles, verify=verify)
+                    if dynamics:
+                        dyn = ude_forecast.latent_dynamics(self.ode, self.latent)
+            fc = ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler,
+                                               quantiles=quantiles, verify=verify)
+            if dynamics:
+                fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
+            return fc
         y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
         if not self.uncertainty:
             n_samples = 1
         yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
-        return ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles,
-                                             verify=verify)
+        fc = ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles,
+                                           verify=verify)
+        if dynamics:
+            dyn = ude_forecast.latent_dynamics(self.ode, self.latent)
+            fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
+        return fc
 
     def _fused_head(self, y_pred, y_true, losses):
         """(nll, reg, per-group prediction mean / std) for this model's latest training prediction:

@@ -45,7 +45,8 @@ EXPORTED_SYMBOLS = ("ude_supported", "ude_query", "ude_pack_weights", "ude_pack_
                     "ude_rhs_eval_vjp", "ude_lincomb", "ude_scaled_sumsq", "ude_build_info",
                     "ude_rk4_forward_ex", "ude_rk4_forward_dec_ex", "ude_rk4_backward_ex", "ude_lincomb_hc",
                     "ude_dopri_ratio", "ude_rk4_forecast_dec", "ude_forecast_summary_workspace",
-                    "ude_forecast_summary", "ude_forecast_verify_workspace", "ude_forecast_verify")
+                    "ude_forecast_summary", "ude_forecast_verify_workspace", "ude_forecast_verify",
+                    "ude_rk4_forecast_dyn")
 SUMSQ_WS = 1025          # doubles of ude_scaled_sumsq's output / workspace (UDE_SUMSQ_WS)
 
 
@@ -193,6 +194,8 @@ class NativeLib:
         L.ude_rk4_backward_ex.restype = i32
         L.ude_rk4_forecast_dec.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, pst, vp]
         L.ude_rk4_forecast_dec.restype = i32
+        L.ude_rk4_forecast_dyn.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, pst, vp]
+        L.ude_rk4_forecast_dyn.restype = i32
         i32s = ctypes.c_int32
         L.ude_forecast_summary_workspace.argtypes = [i32s, i32s, i32s, i32s, i32s, ctypes.POINTER(ctypes.c_int64)]
         L.ude_forecast_summary_workspace.restype = i32
@@ -365,6 +368,11 @@ class NativeLib:
                      stream) -> None:
         check(self.lib.ude_rk4_forecast_dec(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
                                             stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forecast_dec")
+
+    def forecast_dyn(self, desc, prob, pack, sched, y0, dec_pack, yhat, dyn, stats_slab, ctl, stats: UdeSideStats,
+                     stream) -> None:
+        check(self.lib.ude_rk4_forecast_dyn(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
+                                            dyn, stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forecast_dyn")
 
     def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
         out = ctypes.c_int64(0)

@@ -17,6 +17,13 @@ tensor the same definitions run on torch fp64 operators.
 (ude_forecast_verify): CRPS, the weighted interval score, interval coverage, the PIT histogram and
 the empirical multibin skill (lib/Metrics.py ``mb_log(bins=True)``'s window on the samples), per day
 and per (day, region).
+
+``solve_decode_dynamics`` is the same solve that also emits what the model has learned about the
+epidemic at every output time (ude_rk4_forecast_dyn): the compartments S, I, R, the rates beta and
+gamma the rate net gives at that state, R_eff = beta S / gamma, and the augmentation flux Fa -- a
+``(C, T, N, R)`` array that ``dynamics_summary`` turns into a ``Dynamics`` by one ``ensemble_summary``
+call.  ``latent_dynamics`` forms the same channels from a written latent (CPU, Bayesian RHS, output
+times between grid points).
 """
 from __future__ import annotations
 
@@ -56,6 +63,60 @@ class Verify:
             raise ValueError(f"Verify: pit_bins {self.pit_bins} (1 to {MAX_PIT_BINS})")
 
 
+DYN_STATE = ("s", "i", "r")
+DYN_RATES = ("beta", "gamma", "r_eff")
+DYN_FLUX = ("fa_s", "fa_i", "fa_r")
+
+
+def dynamics_names(ode) -> Tuple[str, ...]:
+    """The channels of ``ode``'s dynamics, in their fixed order: ``s, i, r`` always, ``beta, gamma,
+    r_eff`` with a rate net (Fp, FaFp), ``fa_s, fa_i, fa_r`` with an augmentation net (Fa, FaFp)."""
+    kind = ode.ode_type
+    return DYN_STATE + (DYN_RATES if kind in ("Fp", "FaFp") else ()) + (DYN_FLUX if kind in ("Fa", "FaFp") else ())
+
+
+@dataclass
+class Dynamics:
+    """Per-(channel, window, day, region) summary of the learned dynamics over the ensemble (fp64):
+    ``names`` (C channel names, ``dynamics_names``), ``mean`` / ``std`` (C, B, T, R) (population std)
+    and ``quantiles`` (Q, C, B, T, R) or None.  ``dyn["r_eff"]`` is that channel's
+    ``(mean (B, T, R), std (B, T, R), quantiles (Q, B, T, R) or None)``.  The rates are the nets' outputs
+    at the state of each output time (unmasked, as the RHS appends them to ``params``), ``r_eff`` =
+    beta * s / gamma per trajectory, ``fa_*`` the raw augmentation flux (as appended to ``tracker``)."""
+    names: Tuple[str, ...]
+    mean: torch.Tensor
+    std: torch.Tensor
+    quantiles: Optional[torch.Tensor] = None
+
+    def __getitem__(self, name: str):
+        c = self.names.index(name)
+        return self.mean[c], self.std[c], (None if self.quantiles is None else self.quantiles[:, c])
+
+    def _tensors(self):
+        return [(n, getattr(self, n)) for n in ("mean", "std", "quantiles") if getattr(self, n) is not None]
+
+    def _map(self, fn) -> "Dynamics":
+        return Dynamics(self.names, **{n: fn(v) for n, v in self._tensors()})
+
+    def cpu(self) -> "Dynamics":
+        """One stacked device-to-host copy."""
+        parts = self._tensors()
+        if not parts[0][1].is_cuda:
+            return self
+        flat = torch.cat([v.reshape(-1) for _, v in parts]).cpu()
+        out, o = {}, 0
+        for n, v in parts:
+            out[n] = flat[o:o + v.numel()].view(v.shape)
+            o += v.numel()
+        return Dynamics(self.names, **out)
+
+    def numpy(self):
+        """dict: ``names`` and the numpy arrays (``quantiles`` None when absent)."""
+        host = self.cpu()
+        return {"names": host.names, "mean": host.mean.numpy(), "std": host.std.numpy(),
+                "quantiles": None if host.quantiles is None else host.quantiles.numpy()}
+
+
 @dataclass
 class Forecast:
     """Per-(window, day, region) summary of an ensemble forecast (fp64 tensors on the forecast's
@@ -69,7 +130,10 @@ class Forecast:
     central 1 - alpha_k interval holds the target), ``pit`` (T, J) (fraction of groups per bin of the
     target's mid-rank; rows sum to 1), and the per-region forms (means over the B windows)
     ``nll_r`` / ``skill_r`` / ``mae_r`` / ``crps_r`` / ``wis_r`` / ``ens_skill_r`` (T, R) and
-    ``coverage_r`` (K, T, R)."""
+    ``coverage_r`` (K, T, R).
+
+    ``dynamics``: the ``Dynamics`` of the same ensemble when it was asked for
+    (``VAE.forecast(dynamics=True)``), else None."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
@@ -88,26 +152,36 @@ class Forecast:
     wis_r: Optional[torch.Tensor] = None
     ens_skill_r: Optional[torch.Tensor] = None
     coverage_r: Optional[torch.Tensor] = None
+    dynamics: Optional[Dynamics] = None
 
     def _map(self, fn):
-        return Forecast(**{f.name: (None if getattr(self, f.name) is None else fn(getattr(self, f.name)))
+        return Forecast(**{f.name: (None if getattr(self, f.name) is None
+                                    else getattr(self, f.name)._map(fn) if f.name == "dynamics"
+                                    else fn(getattr(self, f.name)))
                            for f in fields(self)})
 
     def cpu(self) -> "Forecast":
-        """One stacked device-to-host copy of every field."""
-        names = [f.name for f in fields(self) if getattr(self, f.name) is not None]
+        """One stacked device-to-host copy of every field (the dynamics' tensors included)."""
+        names = [f.name for f in fields(self) if f.name != "dynamics" and getattr(self, f.name) is not None]
         parts = [getattr(self, n) for n in names]
         if not parts[0].is_cuda:
             return self
-        flat = torch.cat([p.reshape(-1) for p in parts]).cpu()
+        dyn = [] if self.dynamics is None else self.dynamics._tensors()
+        flat = torch.cat([p.reshape(-1) for p in parts + [v for _, v in dyn]]).cpu()
         out, o = {}, 0
         for n, p in zip(names, parts):
             out[n] = flat[o:o + p.numel()].view(p.shape)
             o += p.numel()
+        if self.dynamics is not None:
+            host = {}
+            for n, v in dyn:
+                host[n] = flat[o:o + v.numel()].view(v.shape)
+                o += v.numel()
+            out["dynamics"] = Dynamics(self.dynamics.names, **host)
         return Forecast(**out)
 
     def numpy(self):
-        """dict of numpy arrays (absent fields None)."""
+        """dict of numpy arrays (absent fields None; ``dynamics``: ``Dynamics.numpy()``'s dict)."""
         host = self.cpu()
         return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
                 for f in fields(host)}
@@ -352,3 +426,109 @@ def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
                                   _fused._ctl(plan, dev).data_ptr(), st, stream)
         ode._record_fused(stats, plan.n_eval, sums=sums)
     return yhat
+
+
+def solve_decode_dynamics(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear,
+                          out: Optional[torch.Tensor] = None
+                          ) -> Optional[Tuple[torch.Tensor, torch.Tensor, Tuple[str, ...]]]:
+    """``solve_decode_forecast`` that also emits the dynamics (ude_rk4_forecast_dyn): ``(y_hat (T, N, R),
+    dyn (C, T, N, R) fp32, names)`` with the channels of ``dynamics_names(ode)`` -- at every output time
+    the state ``latent[..., :3]``, the rate net's beta / gamma at that state and ``r_eff = beta * s /
+    gamma`` (fp32), the augmentation net's raw Fa -- or None where ``solve_decode_forecast`` gives None
+    and for a Bayesian RHS (the evaluation at the last output time is not one of the solve's, so it has
+    no weight sample).  ``y_hat`` and the side statistics recorded on ``ode`` are ``solve_decode_forecast``'s
+    bit for bit: the evaluation at the last output time is not counted.  ``out``: a contiguous fp32
+    (C, T, N, R) tensor on y0's device to receive ``dyn`` (exactly its C * T * N * R floats are written)."""
+    if getattr(ode, "uncertainty", "none") == "bayes" or not decoder_head.eligible(ode, y0, linear):
+        return None
+    with torch.no_grad(), torch.cuda.device(y0.device):
+        plan = _forecast_plan(ode, y0, t, step_size)
+        if plan.out_k is None:
+            return None
+        dev = y0.device
+        stream = _fused._stream(dev)
+        sz = plan.sizes
+        y0 = y0.detach().contiguous()
+        params = []
+        for lin in ode.ude_linears():
+            params += [lin.weight, lin.bias]
+        pack = _fused.packed_weights(plan, params, dev)
+        Wd, bd = linear.weight.detach().contiguous(), linear.bias.detach().contiguous()
+        dec_pack = torch.empty(sz.dec_pack_bytes // 4, dtype=torch.float32, device=dev)
+        plan.lib.pack_decoder(plan.desc, Wd.data_ptr(), bd.data_ptr(), dec_pack.data_ptr(), stream)
+        N, R, L = y0.shape
+        names = dynamics_names(ode)
+        yhat = torch.empty((plan.n_times, N, R), dtype=torch.float32, device=dev)
+        shape = (len(names), plan.n_times, N, R)
+        if out is None:
+            dyn = torch.empty(shape, dtype=torch.float32, device=dev)
+        else:
+            if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                raise ValueError(f"solve_decode_dynamics: out must be a contiguous fp32 {shape} tensor on {dev}")
+            dyn = out
+        stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
+        stats, sums, st = _fused._stats_out(plan, dev)
+        with _fused._timed("forecast_dyn"):
+            plan.lib.forecast_dyn(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
+                                  dec_pack.data_ptr(), yhat.data_ptr(), dyn.data_ptr(), stats_slab.data_ptr(),
+                                  _fused._ctl(plan, dev).data_ptr(), st, stream)
+        ode._record_fused(stats, plan.n_eval, sums=sums)
+    return yhat, dyn, names
+
+
+def _mean_stack(stack, h: torch.Tensor) -> torch.Tensor:
+    """A net's layers on ``h`` (N, R * L): Linears as they are, variational layers at their mean weights."""
+    for m in stack:
+        if isinstance(m, torch.nn.Flatten):
+            continue
+        if hasattr(m, "w_mean"):
+            h = torch.nn.functional.linear(h, m.w_mean, m.b_mean)
+        else:
+            h = m(h)
+    return h
+
+
+def latent_dynamics(ode, latent: torch.Tensor) -> Tuple[torch.Tensor, Tuple[str, ...]]:
+    """The channels of ``solve_decode_dynamics`` from a written latent (T, N, R, L), in its dtype:
+    ``(dyn (C, T, N, R), names)``.  The state is ``latent[..., :3]``; the nets are evaluated once at every
+    output state without touching ``ode.params`` / ``ode.tracker`` (on a HIP device by the evaluation
+    kernel, ude_amd/eval_rhs.py, else by the module's layers); ``r_eff = beta * s / gamma`` in the latent's
+    dtype.  A Bayesian RHS is evaluated at its MEAN weights (no draw is taken from its stream): the
+    rates and flux of the posterior mean network, not of the per-evaluation samples of the solve."""
+    names = dynamics_names(ode)
+    with torch.no_grad():
+        lat = latent.detach()
+        T, N, R, L = lat.shape
+        x = lat.reshape(T * N, R, L).contiguous()
+        bayes = getattr(ode, "uncertainty", "none") == "bayes"
+        rates = fa = None
+        from . import eval_rhs
+        if x.is_cuda and eval_rhs.eligible(ode, x):
+            weights = [w.detach() for w in (ode.ude_mean_std()[0] if bayes else
+                                            [p for lin in ode.ude_linears() for p in (lin.weight, lin.bias)])]
+            _f, rates, fa = eval_rhs.rhs_eval(ode, x, weights)
+        else:
+            h = x.reshape(T * N, R * L)
+            if "beta" in names:
+                rates = torch.abs(_mean_stack(ode.Fp_net if bayes else ode._p_stack(), h)).reshape(T * N, R, 2)
+            if "fa_s" in names:
+                fa = _mean_stack(ode.aug_net if bayes else ode._a_stack(), h).reshape(T * N, R, 3)
+        ch = [x[..., 0], x[..., 1], x[..., 2]]
+        if "beta" in names:
+            ch += [rates[..., 0], rates[..., 1], rates[..., 0] * x[..., 0] / rates[..., 1]]
+        if "fa_s" in names:
+            ch += [fa[..., 0], fa[..., 1], fa[..., 2]]
+        dyn = torch.stack(ch).reshape(len(names), T, N, R)
+    return dyn, names
+
+
+def dynamics_summary(dyn: torch.Tensor, names: Sequence[str], n_samples: int, batch: int,
+                     quantiles: Optional[Sequence[float]] = None) -> Dynamics:
+    """``Dynamics`` of ``dyn`` (C, T, S*B, R): one ``ensemble_summary`` of the stacked channels
+    ``(C*T, S*B, R)``, without scale or targets."""
+    C, T, N, R = (int(v) for v in dyn.shape)
+    fc = ensemble_summary(dyn.reshape(C * T, N, R), n_samples, batch, quantiles=quantiles)
+    B = int(batch)
+    quant = None if fc.quantiles is None else fc.quantiles.view(-1, B, C, T, R).permute(0, 2, 1, 3, 4)
+    return Dynamics(tuple(names), fc.mean.view(B, C, T, R).permute(1, 0, 2, 3),
+                    fc.std.view(B, C, T, R).permute(1, 0, 2, 3), quant)

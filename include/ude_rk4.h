@@ -369,6 +369,27 @@ int ude_rk4_forecast_dec(const UdeModelDesc* m, const UdeProblem* p, const float
                          const float* y0, const float* dec_pack, float* yhat, double* stats_slab, uint32_t* ctl,
                          const UdeSideStats* stats, ude_stream_t stream);
 
+/* ude_rk4_forecast_dyn: ude_rk4_forecast_dec (same arguments, the same bits in y_hat and the side
+ * statistics) that also writes the dynamics of every output time, dyn (C, T, N, R) fp32, channel order
+ *   s, i, r                 latent[..., :3] at that time (the fp32 rounding of the solve's state)
+ *   beta, gamma, r_eff      kinds with a rate net (Fp, FaFp): the rates the RHS appends to `params`
+ *                           evaluated at that state (lib/models.py:120-127, unmasked), and
+ *                           r_eff = (beta * s) / gamma in fp32, one IEEE division, no clamp
+ *   fa_s, fa_i, fa_r        kinds with an augmentation net (Fa, FaFp): what the RHS appends to
+ *                           `tracker` (before Fa_w and the mask)
+ * so C = UDE_DYN_CHANNELS(kind): 6 for Fp, 6 for Fa, 9 for FaFp; there is no query, C follows from the
+ * kind.  (C*T, N, R) is directly what ude_forecast_summary reads.  The last output time ends the last
+ * step, so its nets are evaluated once more on the final state; that evaluation is not part of the side
+ * statistics, which stay those of the solve (4 * n_steps evaluations).  Deterministic kinds only
+ * (UDE_E_UNSUPPORTED with UDE_KIND_BAYES: no weight sample of the solve belongs to that evaluation) and,
+ * as for ude_rk4_forecast_dec, not with UdeProblem.recompute.  Rows n >= n_traj do not exist: exactly
+ * C * T * n_traj * R floats are written.  Replaces the (T, N, R, L) latent of the inference odeint plus
+ * one RHS module call per output time (each of which appends to `params` / `tracker`). */
+#define UDE_DYN_CHANNELS(kind) (3 + (((kind) & UDE_KIND_FP) ? 3 : 0) + (((kind) & UDE_KIND_FA) ? 3 : 0))
+int ude_rk4_forecast_dyn(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,
+                         const float* y0, const float* dec_pack, float* yhat, float* dyn, double* stats_slab,
+                         uint32_t* ctl, const UdeSideStats* stats, ude_stream_t stream);
+
 /* Ensemble summary of y_hat (T, S*B, R) (sample n = s*B + b; no model): for every group (t, b, r) the S
  * values v_s = (double)y_hat[t, s*B+b, r] * scale[r] give mean, population std (ddof 0, two passes) and
  * quant[k] = numpy.quantile(v, q[k]) ('linear'; S <= 1024 when n_q > 0, NaN inputs undefined); with

@@ -13,11 +13,20 @@ runs each, wall clock between device synchronisations:
       (ude_forecast_verify in place of ude_forecast_summary).  (b), (c) and (d) alternate run by run,
       so their summary times come from the same minutes of the device.
 
+``--dynamics`` times the forecast's dynamics (S, I, R, beta, gamma, R_eff, Fa per day) instead, three
+paths taking turns:
+
+  (a) latent route: model(x, t, 128, training=False) (the plain inference solve writes the latent), one
+      evaluation-kernel call per output time on latent[j] (ude_amd.eval_rhs.rhs_eval), the channels stacked
+      by torch operators, then the two summaries and their host copies;
+  (b) fused: model.forecast(x, t, 128, y_true, scaler, dynamics=True).cpu();
+  (c) the forecast without dynamics, (b) of the default mode, for the solve kernel's time without DYN.
+
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
 (ude_amd.fused.EVENTS).  Prints one JSON line.
 
-    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128]
+    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128] [--dynamics]
 """
 import argparse
 import importlib
@@ -82,6 +91,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--samples", type=int, default=128)
+    ap.add_argument("--dynamics", action="store_true", help="time the dynamics paths instead (see the docstring)")
     a = ap.parse_args()
     R, B, S, window = 49, a.batch, a.samples, 8
     torch.manual_seed(0)
@@ -116,6 +126,62 @@ def main():
 
     fusedf = fused_with()
 
+    def commit_of():
+        try:
+            return subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True,
+                                  text=True).stdout.strip() or None
+        except OSError:
+            return None
+
+    if a.dynamics:
+        from ude_amd import eval_rhs
+        from ude_amd import forecast as fcast
+        T, names = len(t), fcast.dynamics_names(model.ode)
+
+        def latent_route(e1=None):
+            with torch.no_grad():
+                y_pred = model(x, t, n_samples=S, training=False)
+                lat, ode = model.latent, model.ode
+                weights = ode._eval_weights()
+                rows = []
+                for j in range(T):
+                    xj = lat[j]
+                    _f, rates, fa = eval_rhs.rhs_eval(ode, xj, weights)
+                    rows.append(torch.stack([xj[..., 0], xj[..., 1], xj[..., 2], rates[..., 0], rates[..., 1],
+                                             rates[..., 0] * xj[..., 0] / rates[..., 1],
+                                             fa[..., 0], fa[..., 1], fa[..., 2]]))
+                dyn = torch.stack(rows, 1).contiguous()                              # (C, T, N, R)
+                yhat = y_pred.permute(2, 1, 0, 3).reshape(T, S * B, R)
+                fc = fcast.ensemble_summary(yhat, S, B, y_true=y_test, scale=scaler)
+                fc.dynamics = fcast.dynamics_summary(dyn, names, S, B)
+                fc = fc.cpu()
+            if e1 is not None:
+                e1.record()
+            return fc
+
+        def fused_dyn(e1=None):
+            fc = model.forecast(x, t, n_samples=S, y_true=y_test, scaler=scaler, dynamics=True).cpu()
+            if e1 is not None:
+                e1.record()
+            return fc
+
+        torch.manual_seed(7)
+        fa_ = latent_route()
+        torch.manual_seed(7)                               # the same draw: the two routes' summaries agree
+        fb_ = fused_dyn()
+        vnorm = lambda v: torch.linalg.vector_norm(v, dim=(1, 2, 3))      # per channel
+        agree = (vnorm(fb_.dynamics.mean - fa_.dynamics.mean) / vnorm(fa_.dynamics.mean).clamp(min=1e-30)).tolist()
+        res_a, res_b, res_c = timed_alternating([latent_route, fused_dyn, fusedf], a.runs, a.warmup)
+        C = len(names)
+        print(json.dumps({"tool": "forecast_timing --dynamics", "commit": commit_of(),
+                          "device": torch.cuda.get_device_name(0),
+                          "shape": {"R": R, "L": 8, "S": S, "B": B, "N": S * B, "T": T, "C": C},
+                          "dyn_bytes": C * T * S * B * R * 4, "latent_bytes": T * S * B * R * 8 * 4,
+                          "channel_mean_rel_diff_fused_vs_latent_route": dict(zip(names, agree)),
+                          "latent_route": res_a, "fused_dynamics": res_b, "fused_no_dynamics": res_c,
+                          "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}))
+        return
+
     torch.manual_seed(7)
     ra = host()
     torch.manual_seed(7)                                   # the same draw: the two paths' scores agree
@@ -127,12 +193,7 @@ def main():
     from ude_amd import _native
     ws = {"summary": _native.prebuilt().forecast_summary_workspace(57, S, B, R, 0),
           "verify": _native.prebuilt().forecast_verify_workspace(57, S, B, R, 0, 11, 10)}
-    try:
-        commit = subprocess.run(["git", "-C", REPO, "rev-parse", "--short", "HEAD"], capture_output=True,
-                                text=True).stdout.strip() or None
-    except OSError:
-        commit = None
-    out = {"tool": "forecast_timing", "commit": commit, "device": torch.cuda.get_device_name(0),
+    out = {"tool": "forecast_timing", "commit": commit_of(), "device": torch.cuda.get_device_name(0),
            "shape": {"R": R, "L": 8, "S": S, "B": B, "N": S * B, "T": 57},
            "latent_path_used_by_forecast": model.latent is not None,
            "scores_rel_diff_fused_vs_host": agree, "host": res_a, "fused": res_b,
