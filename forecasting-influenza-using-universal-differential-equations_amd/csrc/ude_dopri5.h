@@ -74,38 +74,6 @@ __device__ __forceinline__ size_t dp_sidx(int n_tiles, int buf, int tile, int wh
   return (((((size_t)buf * n_tiles + tile) * 2 + which) * F + f) * TT) + t;
 }
 
-// Flux of one (trajectory, region) pair from the record's final-layer outputs
-// (lib/models.py:130-150: |rates| -> SIR flux, + fa_w * Fa, masked outside [-1, 2]);
-// accumulates the tracked side statistics (params / tracker) of this evaluation.
-template <class M>
-__device__ __forceinline__ void dp_flux(const float* rec, int r, bool valid, float fa_w, const float (&Y)[3],
-                                        float (&f)[3], double (&st)[5]) {
-  f[0] = f[1] = f[2] = 0.f;
-  if constexpr (M::HAS_P) {
-    const float q0 = rec[M::act_off(0, M::nl(0) - 1) + 2 * r];
-    const float q1 = rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1];
-    const float b = fabsf(q0), gm = fabsf(q1);
-    const float plus = (b * Y[0]) * Y[1];
-    const float minus = gm * Y[1];
-    f[0] = -plus; f[1] = plus - minus; f[2] = minus;
-    if (valid) {
-      st[0] += (double)b; st[1] += (double)gm;
-      st[2] += (double)b * (double)b; st[3] += (double)gm * (double)gm;
-    }
-  }
-  if constexpr (M::HAS_A) {
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-      const float fa = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
-      if constexpr (M::HAS_P) f[c] = f[c] + fa_w * fa;
-      else f[c] = fa;
-      if (valid) st[4] += (double)fa * (double)fa;
-    }
-  }
-#pragma unroll
-  for (int c = 0; c < 3; ++c) f[c] = (Y[c] > 2.f || Y[c] < -1.f) ? 0.f : f[c];
-}
-
 // torchdiffeq _interp_fit + _interp_evaluate for one element (fp32, its op order)
 __device__ __forceinline__ float dp_interp(float y0, float y1, float ym, float f0, float f1, float dt, float x) {
   const float a = ((2.f * dt) * (f1 - f0) - 8.f * (y1 + y0)) + 16.f * ym;
@@ -243,10 +211,28 @@ __device__ void dopri_body(const DArgs& A, float* lds) {
           const int r = p / TT, t = p - r * TT, n = n0 + t;
           const bool valid = n < A.n_traj;
           float* rec = lds + t * SR;
-          float Y[3], f[3];
+          // this evaluation's flux and its share of the tracked side statistics (params / tracker)
+          float Y[3], f[3] = {};
 #pragma unroll
           for (int c = 0; c < 3; ++c) Y[c] = rec[M::Y_OFF + 3 * r + c];
-          dp_flux<M>(rec, r, valid, A.fa_w, Y, f, st);
+          if constexpr (M::HAS_P) {
+            float b, gm;
+            sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
+            if (valid) {
+              st[0] += (double)b; st[1] += (double)gm;
+              st[2] += (double)b * (double)b; st[3] += (double)gm * (double)gm;
+            }
+          }
+          if constexpr (M::HAS_A) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+              const float fa = rec[FA_OUT<M> + 3 * r + c];
+              sir_add_fa<M::HAS_P>(f[c], A.fa_w, fa);
+              if (valid) st[4] += (double)fa * (double)fa;
+            }
+          }
+#pragma unroll
+          for (int c = 0; c < 3; ++c) f[c] = sir_masked(Y[c]) ? 0.f : f[c];
           if constexpr (MODE == dp::MODE_F0) {
 #pragma unroll
             for (int c = 0; c < 3; ++c) {

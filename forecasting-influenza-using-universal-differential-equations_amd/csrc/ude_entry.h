@@ -9,6 +9,7 @@
 //  - a new forward entry (another set of outputs): a thin function like forward / forward_dec /
 //    forecast_dec that validates, fills the KArgs fields only it has, and calls launch_forward.
 //  - a persistent kernel's grid: occupancy_grid.
+//  - a change to the right-hand side: ude_sir.h, and the oracle restatements.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>

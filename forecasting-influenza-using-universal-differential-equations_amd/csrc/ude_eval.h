@@ -47,27 +47,20 @@ __device__ __forceinline__ void eval_f_pairs(const float* lds, const EArgs& A, i
   for (int i = threadIdx.x; i < nvalid; i += NTHREADS) {
     const int t = i / M::R, r = i - t * M::R;
     const float* rec = lds + t * SR;
-    float Y[3], f[3];
+    float Y[3], f[3] = {};
 #pragma unroll
     for (int c = 0; c < 3; ++c) Y[c] = rec[M::Y_OFF + 3 * r + c];
     if constexpr (M::HAS_P) {
-      const float b = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r]);
-      const float gm = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1]);
-      const float plus = (b * Y[0]) * Y[1];
-      const float minus = gm * Y[1];
-      f[0] = -plus; f[1] = plus - minus; f[2] = minus;
+      float b, gm;
+      sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
     }
     if constexpr (M::HAS_A) {
 #pragma unroll
-      for (int c = 0; c < 3; ++c) {
-        const float v = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
-        if constexpr (M::HAS_P) f[c] = f[c] + A.fa_w * v;
-        else f[c] = v;
-      }
+      for (int c = 0; c < 3; ++c) sir_add_fa<M::HAS_P>(f[c], A.fa_w, rec[FA_OUT<M> + 3 * r + c]);
     }
     float* dst = out + ((size_t)n0 * M::R + i) * M::L;
 #pragma unroll
-    for (int c = 0; c < 3; ++c) dst[c] = scale * ((Y[c] > 2.f || Y[c] < -1.f) ? 0.f : f[c]);
+    for (int c = 0; c < 3; ++c) dst[c] = scale * (sir_masked(Y[c]) ? 0.f : f[c]);
     for (int c = 3; c < M::L; ++c) dst[c] = 0.f;
   }
 }
@@ -103,15 +96,12 @@ __device__ void eval_fwd_body(const EArgs& A, float* lds) {
       const int r = p / TT, t = p - r * TT, n = n0 + t;
       if (n >= A.n_traj) continue;
       const float* rec = lds + t * SR;
-      float Y[3], f[3];
+      float Y[3], f[3] = {};
 #pragma unroll
       for (int c = 0; c < 3; ++c) Y[c] = rec[M::Y_OFF + 3 * r + c];
       if constexpr (M::HAS_P) {
-        const float b = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r]);
-        const float gm = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1]);
-        const float plus = (b * Y[0]) * Y[1];
-        const float minus = gm * Y[1];
-        f[0] = -plus; f[1] = plus - minus; f[2] = minus;
+        float b, gm;
+        sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
         if (A.rates) {
           A.rates[((size_t)n * M::R + r) * 2] = b;
           A.rates[((size_t)n * M::R + r) * 2 + 1] = gm;
@@ -120,15 +110,14 @@ __device__ void eval_fwd_body(const EArgs& A, float* lds) {
       if constexpr (M::HAS_A) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-          const float v = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
-          if constexpr (M::HAS_P) f[c] = f[c] + A.fa_w * v;
-          else f[c] = v;
+          const float v = rec[FA_OUT<M> + 3 * r + c];
+          sir_add_fa<M::HAS_P>(f[c], A.fa_w, v);
           if (A.fa) A.fa[((size_t)n * M::R + r) * 3 + c] = v;
         }
       }
       float* dst = A.f + ((size_t)n * M::R + r) * M::L;
 #pragma unroll
-      for (int c = 0; c < 3; ++c) dst[c] = (Y[c] > 2.f || Y[c] < -1.f) ? 0.f : f[c];
+      for (int c = 0; c < 3; ++c) dst[c] = sir_masked(Y[c]) ? 0.f : f[c];
       for (int c = 3; c < M::L; ++c) dst[c] = 0.f;
     }
     __syncthreads();
@@ -164,8 +153,8 @@ struct EvalEp {
 template <class M, int SR>
 __device__ __forceinline__ void eval_flux_backward(float* lds, const EArgs& A, int n0) {
   constexpr int RG = (M::R + 3) / 4, ITEMS = TT * RG;
-  constexpr int QO = M::HAS_P ? M::act_off(0, M::nl(0) - 1) : 0, QG = M::HAS_P ? M::gbuf(0, M::nl(0) - 1) : 0;
-  constexpr int FO = M::HAS_A ? M::act_off(1, M::nl(1) - 1) : 0, FG = M::HAS_A ? M::gbuf(1, M::nl(1) - 1) : 0;
+  constexpr int QO = Q_OUT<M>, QG = M::HAS_P ? M::gbuf(0, M::nl(0) - 1) : 0;
+  constexpr int FG = M::HAS_A ? M::gbuf(1, M::nl(1) - 1) : 0;
   #pragma unroll 1
   for (int it = threadIdx.x; it < ITEMS; it += NTHREADS) {
     const int t = it & (TT - 1), rg = it >> 4;
@@ -184,33 +173,20 @@ __device__ __forceinline__ void eval_flux_backward(float* lds, const EArgs& A, i
       for (int c = 0; c < 3; ++c) {
         Y[c] = rec[M::Y_OFF + 3 * r + c];
         const float dk = rec[M::RK_DK1 + 3 * r + c];
-        dres[c] = (!live || Y[c] > 2.f || Y[c] < -1.f) ? 0.f : dk;
+        dres[c] = (!live || sir_masked(Y[c])) ? 0.f : dk;
       }
       if constexpr (M::HAS_A) {
 #pragma unroll
-        for (int c = 0; c < 3; ++c) {
-          const float d = M::HAS_P ? A.fa_w * dres[c] : dres[c];
-          rec[FG + 3 * r + c] = live ? d + rec[M::RK_DK3 + 3 * r + c] : 0.f;
-        }
+        for (int c = 0; c < 3; ++c)
+          rec[FG + 3 * r + c] = sir_fa_cot<M::HAS_P>(live, A.fa_w, dres[c], rec[M::RK_DK3 + 3 * r + c]);
       }
       if constexpr (M::HAS_P) {
         const float q0 = rec[QO + 2 * r], q1 = rec[QO + 2 * r + 1];
-        const float b = fabsf(q0), gm = fabsf(q1);
-        const float dplus = dres[1] - dres[0];
-        const float dminus = dres[2] - dres[1];
-        const float dpi = dplus * Y[1];
-        float dbeta = dpi * Y[0];
-        float dgam = dminus * Y[1];
-        dyf[3 * j] = dpi * b;
-        dyf[3 * j + 1] = dplus * (b * Y[0]) + dminus * gm;
-        if (live) {
-          dbeta += rec[M::RK_DK2 + 2 * r];
-          dgam += rec[M::RK_DK2 + 2 * r + 1];
-        } else {
-          dbeta = 0.f; dgam = 0.f;
-        }
-        rec[QG + 2 * r] = q0 > 0.f ? dbeta : (q0 < 0.f ? -dbeta : 0.f);
-        rec[QG + 2 * r + 1] = q1 > 0.f ? dgam : (q1 < 0.f ? -dgam : 0.f);
+        float b, gm, dbeta, dgam;
+        sir_rates(q0, q1, b, gm);
+        sir_flux_vjp(Y[0], Y[1], b, gm, dres, dbeta, dgam, dyf[3 * j], dyf[3 * j + 1]);
+        rec[QG + 2 * r] = sir_abs_cot(q0, live ? dbeta + rec[M::RK_DK2 + 2 * r] : 0.f);
+        rec[QG + 2 * r + 1] = sir_abs_cot(q1, live ? dgam + rec[M::RK_DK2 + 2 * r + 1] : 0.f);
       }
     }
     // direct part of dx (the MLP part is added by the layer-0 epilogue)

@@ -29,6 +29,7 @@
 #include <utility>
 #include <type_traits>
 #include "ude_model.h"
+#include "ude_sir.h"
 
 namespace ude {
 
@@ -802,6 +803,11 @@ __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
   if (ln == 0) *A.ctl = 0u;
 }
 
+// The nets' final-layer outputs in a trajectory's record behind mlp_forward: the rate net's q at
+// Q_OUT + 2 r (HAS_P) and the augmentation net's raw Fa at FA_OUT + 3 r (HAS_A), region r
+template <class M> constexpr int Q_OUT = M::HAS_P ? M::act_off(0, M::nl(0) - 1) : 0;
+template <class M> constexpr int FA_OUT = M::HAS_A ? M::act_off(1, M::nl(1) - 1) : 0;
+
 // ============================================================================
 // Forward solve
 // ============================================================================
@@ -916,16 +922,16 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             dst[CS] = rec[M::Y_OFF + 3 * r + 1];
             dst[2 * CS] = rec[M::Y_OFF + 3 * r + 2];
             if constexpr (M::HAS_P) {
-              const float b = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r]);
-              const float gm = fabsf(rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1]);
+              float b, gm;
+              sir_rates(rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], b, gm);
               dst[3 * CS] = b;
               dst[4 * CS] = gm;
-              dst[5 * CS] = (b * s) / gm;
+              dst[5 * CS] = sir_r_eff(b, s, gm);
             }
             if constexpr (M::HAS_A) {
               constexpr int c0 = M::HAS_P ? 6 : 3;
 #pragma unroll
-              for (int c = 0; c < 3; ++c) dst[(c0 + c) * CS] = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
+              for (int c = 0; c < 3; ++c) dst[(c0 + c) * CS] = rec[FA_OUT<M> + 3 * r + c];
             }
           }
         }
@@ -1076,12 +1082,8 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
                 for (int c = M::F; c < M::F16; ++c) xrow[c] = 0.f;
             }
             if constexpr (M::HAS_P) {
-              const float q0 = rec[M::act_off(0, M::nl(0) - 1) + 2 * r];
-              const float q1 = rec[M::act_off(0, M::nl(0) - 1) + 2 * r + 1];
-              const float b = fabsf(q0), gm = fabsf(q1);
-              const float plus = (b * Y[0]) * Y[1];
-              const float minus = gm * Y[1];
-              f[0] = -plus; f[1] = plus - minus; f[2] = minus;
+              float b, gm;
+              sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
               if (valid && UDE_ABL != 14) {
                 st_b += (double)b; st_g += (double)gm;
                 st_bb += (double)b * (double)b; st_gg += (double)gm * (double)gm;
@@ -1090,14 +1092,13 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             if constexpr (M::HAS_A) {
 #pragma unroll
               for (int c = 0; c < 3; ++c) {
-                const float fa = rec[M::act_off(1, M::nl(1) - 1) + 3 * r + c];
-                if constexpr (M::HAS_P) f[c] = f[c] + A.fa_w * fa;
-                else f[c] = fa;
+                const float fa = rec[FA_OUT<M> + 3 * r + c];
+                sir_add_fa<M::HAS_P>(f[c], A.fa_w, fa);
                 if (valid && UDE_ABL != 14) st_fa += (double)fa * (double)fa;
               }
             }
 #pragma unroll
-            for (int c = 0; c < 3; ++c) f[c] = (Y[c] > 2.f || Y[c] < -1.f) ? 0.f : f[c];
+            for (int c = 0; c < 3; ++c) f[c] = sir_masked(Y[c]) ? 0.f : f[c];
             float Yn[3];
             const double dd = (double)dt;
             if (j == 0) {
@@ -1740,8 +1741,8 @@ template <class M, int SR>
 __device__ __forceinline__ void flux_backward(float* lds, const KArgs& A, int n0, int jj, float dt,
                                               const float* ca, const float* cb, const float* mu, float cn) {
   constexpr int RG = (M::R + 3) / 4, ITEMS = TT * RG;
-  constexpr int QO = M::HAS_P ? M::act_off(0, M::nl(0) - 1) : 0, QG = M::HAS_P ? M::gbuf(0, M::nl(0) - 1) : 0;
-  constexpr int FO = M::HAS_A ? M::act_off(1, M::nl(1) - 1) : 0, FG = M::HAS_A ? M::gbuf(1, M::nl(1) - 1) : 0;
+  constexpr int QO = Q_OUT<M>, QG = M::HAS_P ? M::gbuf(0, M::nl(0) - 1) : 0;
+  constexpr int FO = FA_OUT<M>, FG = M::HAS_A ? M::gbuf(1, M::nl(1) - 1) : 0;
   constexpr bool VEC_Q = !M::HAS_P || M::QW <= M::kout(0, M::nl(0) - 1);
   constexpr bool VEC_F = !M::HAS_A || M::F4 <= M::kout(1, M::nl(1) - 1);
   // G regions per item: 4 (12 features, 8 rates: 16-B LDS ops), or all of them when R < 4 (one
@@ -1801,15 +1802,14 @@ __device__ __forceinline__ void flux_backward(float* lds, const KArgs& A, int n0
 #pragma unroll
     for (int i = 0; i < NF; ++i) {
       const bool live = valid && i < 3 * G && (4 * rg + i / 3) < M::R;
-      dres[i] = (!live || Y[i] > 2.f || Y[i] < -1.f) ? 0.f : dk[i];
+      dres[i] = (!live || sir_masked(Y[i])) ? 0.f : dk[i];
     }
     if constexpr (M::HAS_A) {
       float dfa[NF];
 #pragma unroll
       for (int i = 0; i < NF; ++i) {
         const bool live = valid && i < 3 * G && (4 * rg + i / 3) < M::R;
-        const float d = M::HAS_P ? A.fa_w * dres[i] : dres[i];
-        dfa[i] = live ? d + cn * fav[i] : 0.f;
+        dfa[i] = sir_fa_cot<M::HAS_P>(live, A.fa_w, dres[i], cn * fav[i]);
       }
       if constexpr (VEC_F) {
 #pragma unroll
@@ -1827,32 +1827,21 @@ __device__ __forceinline__ void flux_backward(float* lds, const KArgs& A, int n0
 #pragma unroll
     for (int i = 0; i < NF; ++i) dyf[i] = 0.f;
     if constexpr (M::HAS_P) {
-      const float* q = qv;
       float dq[NR];
 #pragma unroll
       for (int i = 0; i < NR; ++i) dq[i] = 0.f;
 #pragma unroll
       for (int j = 0; j < G; ++j) {
         const bool live = valid && (4 * rg + j) < M::R;
-        const float* y = Y + 3 * j;
-        const float* dr = dres + 3 * j;
-        const float q0 = q[2 * j], q1 = q[2 * j + 1];
-        const float b = fabsf(q0), gm = fabsf(q1);
-        const float dplus = dr[1] - dr[0];
-        const float dminus = dr[2] - dr[1];
-        const float dpi = dplus * y[1];                 // d(beta*S)
-        float dbeta = dpi * y[0];
-        dyf[3 * j] = dpi * b;
-        dyf[3 * j + 1] = dplus * (b * y[0]) + dminus * gm;
-        float dgam = dminus * y[1];
-        if (live) {
-          dbeta += ca[0] + cb[0] * (b - mu[0]);
-          dgam += ca[1] + cb[1] * (gm - mu[1]);
-        } else {
-          dbeta = 0.f; dgam = 0.f;
-        }
-        dq[2 * j] = q0 > 0.f ? dbeta : (q0 < 0.f ? -dbeta : 0.f);
-        dq[2 * j + 1] = q1 > 0.f ? dgam : (q1 < 0.f ? -dgam : 0.f);
+        const float dr[3] = {dres[3 * j], dres[3 * j + 1], dres[3 * j + 2]};
+        float b, gm, dbeta, dgam;
+        sir_rates(qv[2 * j], qv[2 * j + 1], b, gm);
+        sir_flux_vjp(Y[3 * j], Y[3 * j + 1], b, gm, dr, dbeta, dgam, dyf[3 * j], dyf[3 * j + 1]);
+        // the side statistics' cotangents reach beta / gamma directly
+        dbeta = live ? dbeta + (ca[0] + cb[0] * (b - mu[0])) : 0.f;
+        dgam = live ? dgam + (ca[1] + cb[1] * (gm - mu[1])) : 0.f;
+        dq[2 * j] = sir_abs_cot(qv[2 * j], dbeta);
+        dq[2 * j + 1] = sir_abs_cot(qv[2 * j + 1], dgam);
       }
       if constexpr (VEC_Q) {
 #pragma unroll
@@ -3066,6 +3055,42 @@ __global__ __launch_bounds__(256) void ude_eps_slab_kernel(const float* __restri
 //   dy0[n][static s] = sum_o W0[o][static s] * G0[n][o] + sum_j dlatent[j][n][static s]
 // with G0[n][o] = sum over every evaluation of the layer-0 output gradient.
 // ============================================================================
+// One trajectory tile of the dW0[:, static] GEMM for the lane's static column (region r, static dim
+// cc; s_ok: not a pad column): acc[o] += G0[tile] (row tile o: K0 x 16 trajectories) x x_static[tile]
+// (16 x the column); MFMA q covers trajectories 4g + q.  The callers own the tile walk; acc goes by value.
+template <class M>
+struct StaticAcc { f4 v[M::K0 / 16]; };
+template <class M>
+__device__ __forceinline__ StaticAcc<M> static_tile_mac(const float* g0buf, const float* y0, int n_traj, int tile, int t,
+                                                        int g, int r, int cc, bool s_ok, StaticAcc<M> acc) {
+  constexpr int NOT = M::K0 / 16;
+  f4 a[NOT];
+#pragma unroll
+  for (int o = 0; o < NOT; ++o)
+    a[o] = *reinterpret_cast<const f4*>(g0buf + ((size_t)tile * M::K0 + o * 16 + t) * TT + 4 * g);
+  float b[4];
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const int n = tile * TT + 4 * g + q;
+    b[q] = (s_ok && n < n_traj) ? y0[((size_t)n * M::R + r) * M::L + 3 + cc] : 0.f;
+  }
+#pragma unroll
+  for (int q = 0; q < 4; ++q)
+#pragma unroll
+    for (int o = 0; o < NOT; ++o) acc.v[o] = mfma4(a[o][q], b[q], acc.v[o]);
+  return acc;
+}
+
+// dparams index (torch order) of dW0[row om of the nets' stacked layer-0 outputs][static column s];
+// -1 for a pad row
+template <class M>
+__device__ __forceinline__ int64_t static_dparam_index(int om, int s) {
+  constexpr int P0 = M::HAS_P ? M::kout(0, 0) : 0;   // rows [0, P0): the rate net; behind them: the augmentation net
+  const int net = om >= P0 ? 1 : 0, o = om - (net ? P0 : 0);
+  if (o >= (net ? M::out_dim(1, 0) : M::out_dim(0, 0))) return -1;
+  return (net ? M::param_w_off(1, 0) : M::param_w_off(0, 0)) + (int64_t)o * M::R * M::L + static_col<M>(s);
+}
+
 // dW0[:, static] split-K partials on MFMA: part[chunk][K0][S16] = sum over the
 // chunk's tiles of G0[tile] (K0 x 16 trajectories) x X_static[tile] (16 x S16).
 // Grid (STATIC_CHUNKS, STATIC_GROUPS): wave w of column group y owns static column tile
@@ -3086,31 +3111,18 @@ __global__ __launch_bounds__(256) void ude_static_partial_kernel(const float* __
   const int s = st * 16 + t;
   const int r = s / (M::L - 3), cc = s - r * (M::L - 3);
   const bool s_ok = s < M::S;
-  f4 acc[NOT];
+  StaticAcc<M> acc;
 #pragma unroll
-  for (int o = 0; o < NOT; ++o) acc[o] = f4zero();
+  for (int o = 0; o < NOT; ++o) acc.v[o] = f4zero();
   #pragma unroll 2
   for (int tile = tb; tile < te; ++tile) {
-    f4 a[NOT];
-#pragma unroll
-    for (int o = 0; o < NOT; ++o)
-      a[o] = *reinterpret_cast<const f4*>(g0buf + ((size_t)tile * M::K0 + o * 16 + t) * TT + 4 * g);
-    float b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = tile * TT + 4 * g + q;
-      b[q] = (s_ok && n < n_traj) ? y0[((size_t)n * M::R + r) * M::L + 3 + cc] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int o = 0; o < NOT; ++o) acc[o] = mfma4(a[o][q], b[q], acc[o]);
+    acc = static_tile_mac<M>(g0buf, y0, n_traj, tile, t, g, r, cc, s_ok, acc);
   }
 #pragma unroll
   for (int o = 0; o < NOT; ++o)
 #pragma unroll
     for (int e = 0; e < 4; ++e)
-      part[((size_t)chunk * M::K0 + o * 16 + 4 * g + e) * M::S16 + st * 16 + t] = acc[o][e];
+      part[((size_t)chunk * M::K0 + o * 16 + 4 * g + e) * M::S16 + st * 16 + t] = acc.v[o][e];
 }
 
 template <class M>
@@ -3119,17 +3131,11 @@ __global__ __launch_bounds__(256) void ude_static_reduce_kernel(const float* __r
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= M::K0 * M::S) return;
   const int om = e / M::S, s = e - om * M::S;
-  int net = 0, o = om;
-  if (!M::HAS_P || om >= (M::HAS_P ? M::kout(0, 0) : 0)) {
-    net = 1;
-    o = om - (M::HAS_P ? M::kout(0, 0) : 0);
-  }
-  const int out = net == 0 ? M::out_dim(0, 0) : M::out_dim(1, 0);
-  if (o >= out) return;
+  const int64_t idx = static_dparam_index<M>(om, s);
+  if (idx < 0) return;
   float v = 0.f;
   for (int c = 0; c < M::STATIC_CHUNKS; ++c) v += part[((size_t)c * M::K0 + om) * M::S16 + s];
-  const int w0 = net == 0 ? M::param_w_off(0, 0) : M::param_w_off(1, 0);
-  dparams[w0 + (size_t)o * M::R * M::L + static_col<M>(s)] = v;
+  dparams[idx] = v;
 }
 
 // d y0[:, static] = G0[tile]^T (16 x K0) x W0SP (K0 x S16) on MFMA, plus the direct
@@ -3269,31 +3275,18 @@ __device__ void static_grad_chunk(const float* __restrict__ g0buf, const float* 
   const int s = st * 16 + t;
   const int r = s / (M::L - 3), cc = s - r * (M::L - 3);
   const bool s_ok = s < M::S;
-  f4 acc[NOT];
+  StaticAcc<M> acc;
 #pragma unroll
-  for (int o = 0; o < NOT; ++o) acc[o] = f4zero();
+  for (int o = 0; o < NOT; ++o) acc.v[o] = f4zero();
   #pragma unroll 4
   for (int tile = tb + w; tile < te; tile += WAVES) {
-    f4 a[NOT];
-#pragma unroll
-    for (int o = 0; o < NOT; ++o)
-      a[o] = *reinterpret_cast<const f4*>(g0buf + ((size_t)tile * M::K0 + o * 16 + t) * TT + 4 * g);
-    float b[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {
-      const int n = tile * TT + 4 * g + q;
-      b[q] = (s_ok && n < n_traj) ? y0[((size_t)n * M::R + r) * M::L + 3 + cc] : 0.f;
-    }
-#pragma unroll
-    for (int q = 0; q < 4; ++q)
-#pragma unroll
-      for (int o = 0; o < NOT; ++o) acc[o] = mfma4(a[o][q], b[q], acc[o]);
+    acc = static_tile_mac<M>(g0buf, y0, n_traj, tile, t, g, r, cc, s_ok, acc);
   }
   // the 4 waves' partial tiles summed in wave order (LDS), written as this chunk's partial
   f4* red = reinterpret_cast<f4*>(lds);
   if (w > 0) {
 #pragma unroll
-    for (int o = 0; o < NOT; ++o) red[((w - 1) * NOT + o) * 64 + lane] = acc[o];
+    for (int o = 0; o < NOT; ++o) red[((w - 1) * NOT + o) * 64 + lane] = acc.v[o];
   }
   __syncthreads();
   unsigned int* flag = reinterpret_cast<unsigned int*>(lds) + 3 * NOT * 256;   // behind the partial tiles
@@ -3303,7 +3296,7 @@ __device__ void static_grad_chunk(const float* __restrict__ g0buf, const float* 
     double* dst = reinterpret_cast<double*>(part + ((size_t)st * TCH + c) * NOT * 256);
 #pragma unroll
     for (int o = 0; o < NOT; ++o) {
-      const f4 v = ((acc[o] + red[o * 64 + lane]) + red[(NOT + o) * 64 + lane]) + red[(2 * NOT + o) * 64 + lane];
+      const f4 v = ((acc.v[o] + red[o * 64 + lane]) + red[(NOT + o) * 64 + lane]) + red[(2 * NOT + o) * 64 + lane];
       __hip_atomic_store(dst + (o * 64 + lane) * 2, __builtin_bit_cast(double, __builtin_shufflevector(v, v, 0, 1)),
                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       __hip_atomic_store(dst + (o * 64 + lane) * 2 + 1, __builtin_bit_cast(double, __builtin_shufflevector(v, v, 2, 3)),
@@ -3336,17 +3329,8 @@ __device__ void static_grad_chunk(const float* __restrict__ g0buf, const float* 
     if (sc >= M::S) continue;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
-      const int om = o * 16 + 4 * (ln >> 4) + e;
-      int net = 0, oo = om;
-      if (!M::HAS_P || om >= (M::HAS_P ? M::kout(0, 0) : 0)) {
-        net = 1;
-        oo = om - (M::HAS_P ? M::kout(0, 0) : 0);
-      }
-      const int out = net == 0 ? M::out_dim(0, 0) : M::out_dim(1, 0);
-      if (oo < out) {
-        const int w0 = net == 0 ? M::param_w_off(0, 0) : M::param_w_off(1, 0);
-        dparams[w0 + (size_t)oo * M::R * M::L + static_col<M>(sc)] = v[e];
-      }
+      const int64_t idx = static_dparam_index<M>(o * 16 + 4 * (ln >> 4) + e, sc);
+      if (idx >= 0) dparams[idx] = v[e];
     }
   }
   if (threadIdx.x == 0) ctl[1 + st] = 0u;
