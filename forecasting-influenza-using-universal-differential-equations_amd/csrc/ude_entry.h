@@ -131,10 +131,6 @@ struct Ops {
     HIPCHK(hipFuncSetAttribute((const void*)&ude_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
     HIPCHK(hipFuncSetAttribute((const void*)&ude_dec_bwd_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                DecBwdDims<M>::LDS));
-    // the static-feature dy0 kernel stages one tile's (16, R, L) time sums of d latent in LDS
-    if (M::HOIST)
-      HIPCHK(hipFuncSetAttribute((const void*)&ude_dy0_static_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                 DY0_STATIC_LDS));
     if constexpr (M::GST)
       HIPCHK(hipFuncSetAttribute((const void*)&ude_gst_dw_kernel<M>, hipFuncAttributeMaxDynamicSharedMemorySize,
                                  Gst<M>::LDS));
@@ -161,20 +157,28 @@ struct Ops {
     return occupancy_grid((const void*)&ude_bwd_kernel<M>, M::BWD_THREADS, M::LDS_B, device, n_tiles, gb, cus);
   }
 
-  // grad-slab workspace tail (HOIST): G0 [tile][K0][16] + split-K partials [chunks][K0][S16]
+  // grad-slab workspace tail (HOIST): G0 [tile][K0][16] + the tail's chunk partials
   static int64_t static_ws_floats(int n_tiles) {
-    if (!M::HOIST) return 0;
-    const int64_t legacy = (int64_t)M::STATIC_CHUNKS * M::K0 * M::S16, tail = Tail<M>::part_floats();
-    return (int64_t)n_tiles * M::K0 * TT + (legacy > tail ? legacy : tail);
+    return M::HOIST ? (int64_t)n_tiles * M::K0 * TT + Tail<M>::part_floats() : 0;
   }
   // ... and where the two parts lie in a slab of gb workgroup slabs (backward, EvalOps::eval_vjp)
   static void static_ws(float* slab, int gb, int n_tiles, float** g0buf, float** part) {
     *g0buf = slab + (size_t)gb * M::SLAB_STRIDE;
     *part = *g0buf + (size_t)n_tiles * M::K0 * TT;
   }
-  // control words of the *_ex calls: [0] the forward's arrival counter, [1 + st] the tail's static
-  // column tiles (include/ude_rk4.h)
+  // control words: [0] the forward's arrival counter, [1 + st] the tail's static column tiles
+  // (include/ude_rk4.h).  A call that is handed none (the older entries, a forecast with ctl = NULL) takes
+  // the spare ones ude_query reserves in its own buffers -- behind the forward's statistics partials,
+  // behind the backward's gradient slab and static workspace (ctl_off, in floats) -- and zeroes them on
+  // its stream first: nothing is allocated, nothing outlives the call.
   static constexpr int64_t CTL_WORDS = 1 + Tail<M>::NST;
+  static constexpr int64_t CTL_BYTES = ((CTL_WORDS * 4 + 63) / 64) * 64;
+  static int64_t ctl_off(int gb, int n_tiles) {
+    return ((int64_t)gb * M::SLAB_STRIDE + static_ws_floats(n_tiles) + 3) & ~(int64_t)3;
+  }
+  static unsigned* spare_ctl(void* at, hipStream_t s) {
+    return hipMemsetAsync(at, 0, CTL_WORDS * 4, s) == hipSuccess ? static_cast<unsigned*>(at) : nullptr;
+  }
 
   // the resident-weight forward (one workgroup per CU) when every tile has a CU of its own;
   // UDE_FWD_RES=0 turns it off, =2 forces it at any batch (A/B measurement)
@@ -247,8 +251,8 @@ struct Ops {
     o->ckpt_bytes = (int64_t)n_tiles * p->n_steps * 4 * (M::F * TT + (M::ACT_STORED ? TT * M::XST_W : 0)) * 4;
     // GST: + the tiles' static features [tile][16][S16] (the weight-gradient GEMM's layer-0 input)
     if (M::GST) o->ckpt_bytes += (int64_t)n_tiles * TT * M::S16 * 4;
-    o->stats_slab_bytes = (int64_t)gf * 5 * 8;
-    o->grad_slab_bytes = (int64_t)gb * M::SLAB_STRIDE * 4 + static_ws_floats(n_tiles) * 4;
+    o->stats_slab_bytes = (int64_t)gf * 5 * 8 + CTL_BYTES;
+    o->grad_slab_bytes = ctl_off(gb, n_tiles) * 4 + CTL_BYTES;
     if constexpr (M::GST) {
       o->grad_slab_bytes = (gst_rows_floats(n_tiles, p->n_steps) +
                             n_evals(p) * gst_ks(cus, n_evals(p), n_tiles) * (int64_t)M::SLAB_TOTAL) * 4;
@@ -266,7 +270,7 @@ struct Ops {
     o->ckpt_final_bytes = (int64_t)n_tiles * M::F * TT * 4;
     o->dec_ws_bytes = (int64_t)gd * LossDims<M::R>::SLAB * 4;
     o->act_bytes = M::ACT_STORED ? (int64_t)n_tiles * p->n_steps * 4 * TT * M::XST_W * 4 : 0;
-    o->ctl_bytes = ((CTL_WORDS * 4 + 63) / 64) * 64;
+    o->ctl_bytes = CTL_BYTES;
     return UDE_OK;
   }
 
@@ -285,7 +289,7 @@ struct Ops {
 
   // Training forward with the decoder epilogue: y_hat (T, N, R) and latent_init_loss instead of the
   // latent; ckpt (ckpt_bytes + ckpt_final_bytes) also receives the final state.
-  // stats: mean / std / fa_norm outputs (sums nullable); ctl: null = the separate finalize launches
+  // stats: mean / std / fa_norm outputs (sums nullable); ctl: null = the spare words of stats_slab
   static int forward_dec(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
                          const float* dec_pack, float* yhat, float* ckpt, double* stats_slab, double* reg_slab,
                          const UdeSideStats* st, unsigned* ctl, float* reg_out, hipStream_t s) {
@@ -498,7 +502,7 @@ struct Ops {
   //            its own (so an inference solve, the forecast included, never splits);
   //   resident else iff fwd_res(): one workgroup per CU, gf = min(n_tiles, cus) (<= the slabs' size);
   //   plain    else.
-  // ctl == null (the legacy entries): the statistics and latent_init_loss are finalized by separate launches.
+  // ctl == null: the spare control words behind stats_slab's grid_fwd partials, zeroed here.
   static int launch_forward(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
                             double* stats_slab, const UdeSideStats* st, unsigned* ctl, KArgs& a, hipStream_t s) {
     int dev = 0;
@@ -511,6 +515,7 @@ struct Ops {
     a.stats_slab = stats_slab;
     a.n_traj = p->n_traj; a.n_steps = p->n_steps; a.n_out = p->n_out; a.n_tiles = n_tiles;
     a.fa_w = p->fa_w;
+    if (!ctl && !(ctl = spare_ctl(stats_slab + (size_t)gf * 5, s))) return UDE_E_HIP;
     const double n_eval = 4.0 * (double)p->n_steps * (double)p->n_traj * (double)M::R;
     set_stats_out(a, st, ctl, n_eval);
     const bool train = a.ckpt != nullptr, dec = a.yhat != nullptr;
@@ -522,21 +527,11 @@ struct Ops {
       HIPCHK(hipLaunchKernel(k, dim3(gf), dim3(threads), args, lds, s));
       return UDE_OK;
     });
-    if (rc) return rc == NO_VARIANT ? UDE_E_UNSUPPORTED : rc;
-    if (!ctl) {
-      hipLaunchKernelGGL(ude_stats_finalize_kernel<0>, dim3(1), dim3(320), 0, s, stats_slab, gf, n_eval, a.o_mean,
-                         a.o_std, a.o_norm);
-      HIPCHK(hipGetLastError());
-      if (a.reg_slab) {
-        hipLaunchKernelGGL(ude_sum_finalize_kernel<0>, dim3(1), dim3(64), 0, s, (const double*)a.reg_slab, gf, a.o_reg);
-        HIPCHK(hipGetLastError());
-      }
-    }
-    return UDE_OK;
+    return rc == NO_VARIANT ? UDE_E_UNSUPPORTED : rc;
   }
 
-  // st: the forward's statistics (read); dst: their cotangents (nullable); ctl: null = the separate
-  // tail launches (grad finalize, static partial / reduce, dy0 static), else the one tail kernel
+  // st: the forward's statistics (read); dst: their cotangents (nullable); ctl: null = the spare words
+  // behind the slab (ctl_off); the GST backward has no tail and uses none
   static int backward(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
                       const float* ckpt, const float* dlatent, const float* dlat_sir, const UdeSideStats* st,
                       const UdeSideStatsGrad* dst, float* dy0, float* slab, unsigned* ctl, float* dparams,
@@ -594,33 +589,11 @@ struct Ops {
     hipLaunchKernelGGL((ude_bwd_kernel<M>), dim3(gb), dim3(M::BWD_THREADS), M::LDS_B, s, a);
     HIPCHK(hipGetLastError());
     HIPCHK(static_tsum(p, dlatent, dy0, s));
-    if (ctl) {
-      hipLaunchKernelGGL((ude_bwd_tail_kernel<M>), dim3(Tail<M>::blocks(n_tiles)), dim3(256), Tail<M>::LDS, s,
-                         (const float*)slab, gb, (const float*)g0buf, pack, y0, dlatent, p->n_traj, n_tiles,
-                         p->n_out + 1, part, ctl, dy0, dparams);
-      HIPCHK(hipGetLastError());
-      return UDE_OK;
-    }
-    hipLaunchKernelGGL((ude_grad_finalize_kernel<M>), dim3((M::SLAB_TOTAL + 63) / 64), dim3(256), 0, s,
-                       (const float*)slab, gb, dparams);
+    if (!ctl && !(ctl = spare_ctl(slab + ctl_off(gb, n_tiles), s))) return UDE_E_HIP;
+    hipLaunchKernelGGL((ude_bwd_tail_kernel<M>), dim3(Tail<M>::blocks(n_tiles)), dim3(256), Tail<M>::LDS, s,
+                       (const float*)slab, gb, (const float*)g0buf, pack, y0, dlatent, p->n_traj, n_tiles,
+                       p->n_out + 1, part, ctl, dy0, dparams);
     HIPCHK(hipGetLastError());
-    if (M::BAYES) {
-      // d |std|: the eps-weighted half of every workgroup slab
-      hipLaunchKernelGGL((ude_grad_finalize_kernel<M>), dim3((M::SLAB_TOTAL + 63) / 64), dim3(256), 0, s,
-                         (const float*)(slab + M::SLAB_TOTAL), gb, dparams + M::N_PARAMS);
-      HIPCHK(hipGetLastError());
-    }
-    if (M::HOIST) {
-      hipLaunchKernelGGL((ude_static_partial_kernel<M>), dim3(M::STATIC_CHUNKS, M::STATIC_GROUPS), dim3(256), 0, s,
-                         (const float*)g0buf, y0, p->n_traj, n_tiles, part);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL((ude_static_reduce_kernel<M>), dim3((M::K0 * M::S + 255) / 256), dim3(256), 0, s,
-                         (const float*)part, dparams);
-      HIPCHK(hipGetLastError());
-      hipLaunchKernelGGL((ude_dy0_static_kernel<M>), dim3(n_tiles), dim3(256), TT * M::R * M::L * 4, s,
-                         (const float*)g0buf, pack, dlatent, p->n_traj, p->n_out + 1, dy0);
-      HIPCHK(hipGetLastError());
-    }
     return UDE_OK;
   }
 };
@@ -842,9 +815,6 @@ struct EvalOps {
     }
   }
   // workspace: dW slab [gb][SLAB_STRIDE], G0 + static partials (HOIST), the tail's ticket words
-  static int64_t ctl_off(int gb, int n_tiles) {
-    return ((int64_t)gb * M::SLAB_STRIDE + Ops<M>::static_ws_floats(n_tiles) + 3) & ~(int64_t)3;
-  }
   static int workspace(const UdeProblem* p, int device, int64_t* bytes) {
     if (M::BAYES) return UDE_E_UNSUPPORTED;      // each evaluation's sample is a deterministic RHS
     if (p->n_traj < 1) return UDE_E_INVALID;
@@ -852,7 +822,7 @@ struct EvalOps {
     int gf = 1, gb = 1;
     int rc = grids(device, n_tiles, &gf, &gb);
     if (rc) return rc;
-    *bytes = (ctl_off(gb, n_tiles) + Ops<M>::CTL_WORDS) * 4;
+    *bytes = (Ops<M>::ctl_off(gb, n_tiles) + Ops<M>::CTL_WORDS) * 4;
     return UDE_OK;
   }
   static int forward(const UdeProblem* p, const float* pack, const float* x, float* f, float* rates, float* fa,
@@ -907,7 +877,7 @@ struct EvalOps {
     a.dx = dx; a.slab = slab; a.g0buf = g0buf;
     a.n_traj = p->n_traj; a.n_tiles = n_tiles; a.fa_w = p->fa_w;
     a.fout = fout; a.f_scale = f_scale;
-    unsigned int* ctl = reinterpret_cast<unsigned int*>(slab + ctl_off(gb, n_tiles));
+    unsigned int* ctl = reinterpret_cast<unsigned int*>(slab + Ops<M>::ctl_off(gb, n_tiles));
     a.ctl = ctl; a.n_ctl = (int)Ops<M>::CTL_WORDS;
     hipLaunchKernelGGL((ude_eval_vjp_kernel<M>), dim3(gb), dim3(eval_vjp_threads<M>()), M::LDS_B, s, a);
     HIPCHK(hipGetLastError());

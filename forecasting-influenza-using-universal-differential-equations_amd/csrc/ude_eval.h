@@ -26,7 +26,7 @@ struct EArgs {
   const float* cot_f;      // VJP: (N, R, L) cotangent of f (dims >= 3 ignored: f is 0 there)
   const float* cot_rates;  // VJP: (N, R, 2) (nullable: zero)
   const float* cot_fa;     // VJP: (N, R, 3) (nullable: zero)
-  float* dx;               // VJP: (N, R, L); static dims written by ude_dy0_static_kernel (HOIST)
+  float* dx;               // VJP: (N, R, L); static dims written by ude_bwd_tail_kernel (HOIST)
   float* slab;             // VJP: per-workgroup dW partials [grid][SLAB_STRIDE]
   float* g0buf;            // VJP: per-trajectory layer-0 output gradients [tile][K0][16] (HOIST)
   int n_traj, n_tiles;
@@ -320,7 +320,7 @@ __device__ void eval_vjp_body(const EArgs& A, float* lds) {
       }
     }
     __syncthreads();
-    // dx (dynamic dims; static dims: ude_dy0_static_kernel from the G0 sums below)
+    // dx (dynamic dims; static dims: ude_bwd_tail_kernel from the G0 sums below)
     {
       const int nvalid = min(TT, A.n_traj - n0) * M::R;    // row-mapped, as the tile start
       #pragma unroll 1

@@ -90,9 +90,9 @@ struct KArgs {
   double* reg_slab;           // DEC forward: per-workgroup latent_init_loss partial sums
   float* ckpt_final;          // DEC training forward: the final-state block (ckpt + ckpt_final_off)
   float* gst;                 // GST backward: layer-output gradient rows [tile][step][stage][16][ACT_A4]
-  // forward: the statistics finalised in the kernel by its last workgroup (ctl != nullptr; the
-  // separate ude_stats_finalize_kernel otherwise)
-  unsigned int* ctl;          // arrival counter, zero on entry, left zero
+  // forward: the statistics finalised in the kernel by its last workgroup (finalize_stats_last)
+  unsigned int* ctl;          // arrival counter, zero on entry, left zero; the host never passes null
+                              // (Ops::launch_forward), fwd_body still tests it (see there)
   float* o_mean;              // 2 floats
   float* o_std;               // 2 floats
   float* o_norm;              // 1 float
@@ -727,9 +727,9 @@ __device__ __forceinline__ double wave_sum(double v) {
 }
 
 // Fixed-order sum of one statistic's per-workgroup partials by one wave (lane-strided, then a fixed
-// butterfly): the order of ude_stats_finalize_kernel / ude_sum_finalize_kernel, so both paths give the
-// same bits.  The partials are read with device-coherent loads (written by other workgroups, possibly
-// on other XCDs, with device-coherent stores).
+// butterfly): the order of ude_stats_finalize_kernel (the dopri5 forward's finalize).  The partials are
+// read with device-coherent loads (written by other workgroups, possibly on other XCDs, with
+// device-coherent stores).
 __device__ __forceinline__ double wave_sum_partials(const double* part, int n, int stride, int off, int ln) {
   double s = 0.0;
   for (int gi = ln; gi < n; gi += 64)
@@ -794,6 +794,12 @@ __device__ __forceinline__ void finalize_stats_last(const KArgs& A, int ln) {
   }
   if (ln == 2 && A.o_norm) A.o_norm[0] = (float)sqrt(tot[4]);
   if (ln == 3 && has_reg) A.o_reg[0] = (float)reg;
+  // o_sums may alias stats_slab[0..4], workgroup 0's partials (ude_rk4_forward / ude_rk4_forward_dec hand
+  // the totals back there).  That is safe, and rests on this function's shape: one wave does all of it,
+  // every other workgroup has stored its partials and left (its ticket is taken), and the value lane c
+  // stores to o_sums[c] is tot[c], whose butterfly has consumed every lane's loads of statistic c --
+  // stats_slab[c] among them, the only partial that store overwrites.  A finalize spread over several
+  // waves, or one that re-read a partial after this store, would break it.
   if (A.o_sums && ln < 5) {
     double v = tot[0];
 #pragma unroll
@@ -1217,8 +1223,8 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
     double s = 0;
     for (int w = 0; w < WAVES; ++w) s += red[w * NS + tid];
     double* dst = tid < 5 ? A.stats_slab + (size_t)blockIdx.x * 5 + tid : A.reg_slab + blockIdx.x;
-    // in-kernel finalize (ctl): device-coherent store, read back by the last workgroup (see
-    // finalize_stats_last)
+    // device-coherent store, read back by the last workgroup (see finalize_stats_last)
+    // A.ctl is never null; the two tests of it here only keep the kernel's register allocation as measured
     if (A.ctl) __hip_atomic_store(dst, s, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     else *dst = s;
   }
@@ -3029,12 +3035,6 @@ __device__ __forceinline__ void grad_finalize_body(const float* __restrict__ sla
     if (e >= 0) dparams[e] = (part[0][lo] + part[1][lo]) + (part[2][lo] + part[3][lo]);
   }
 }
-template <class M>
-__global__ __launch_bounds__(256) void ude_grad_finalize_kernel(const float* __restrict__ slab, int ngrid,
-                                                                float* __restrict__ dparams) {
-  __shared__ float part[4][64];
-  grad_finalize_body<M>(slab, ngrid, dparams, blockIdx.x, part);
-}
 
 // BAYES: the eps stream ([eval][N_PARAMS], torch order) re-laid out per evaluation in
 // slab order (dW tiles in MFMA C order, bias rows), the layout the backward weights
@@ -3089,53 +3089,6 @@ __device__ __forceinline__ int64_t static_dparam_index(int om, int s) {
   const int net = om >= P0 ? 1 : 0, o = om - (net ? P0 : 0);
   if (o >= (net ? M::out_dim(1, 0) : M::out_dim(0, 0))) return -1;
   return (net ? M::param_w_off(1, 0) : M::param_w_off(0, 0)) + (int64_t)o * M::R * M::L + static_col<M>(s);
-}
-
-// dW0[:, static] split-K partials on MFMA: part[chunk][K0][S16] = sum over the
-// chunk's tiles of G0[tile] (K0 x 16 trajectories) x X_static[tile] (16 x S16).
-// Grid (STATIC_CHUNKS, STATIC_GROUPS): wave w of column group y owns static column tile
-// 4y + w (every wave of the chip busy: the K0 x S16 x N GEMM is MFMA-issue bound);
-// MFMA q covers trajectories 4g + q.  Tiles are walked two at a time so the next tile's
-// operand loads are in flight during this tile's MFMAs.
-template <class M>
-__global__ __launch_bounds__(256) void ude_static_partial_kernel(const float* __restrict__ g0buf,
-                                                                 const float* __restrict__ y0, int n_traj,
-                                                                 int n_tiles, float* __restrict__ part) {
-  constexpr int NOT = M::K0 / 16, NST = M::S16 / 16;
-  const int w = threadIdx.x >> 6, lane = threadIdx.x & 63, t = lane & 15, g = lane >> 4;
-  const int st = blockIdx.y * 4 + w;
-  if (st >= NST) return;                             // no barriers or LDS in this kernel
-  const int chunk = blockIdx.x;
-  const int per = (n_tiles + M::STATIC_CHUNKS - 1) / M::STATIC_CHUNKS;
-  const int tb = chunk * per, te = min(n_tiles, tb + per);
-  const int s = st * 16 + t;
-  const int r = s / (M::L - 3), cc = s - r * (M::L - 3);
-  const bool s_ok = s < M::S;
-  StaticAcc<M> acc;
-#pragma unroll
-  for (int o = 0; o < NOT; ++o) acc.v[o] = f4zero();
-  #pragma unroll 2
-  for (int tile = tb; tile < te; ++tile) {
-    acc = static_tile_mac<M>(g0buf, y0, n_traj, tile, t, g, r, cc, s_ok, acc);
-  }
-#pragma unroll
-  for (int o = 0; o < NOT; ++o)
-#pragma unroll
-    for (int e = 0; e < 4; ++e)
-      part[((size_t)chunk * M::K0 + o * 16 + 4 * g + e) * M::S16 + st * 16 + t] = acc.v[o][e];
-}
-
-template <class M>
-__global__ __launch_bounds__(256) void ude_static_reduce_kernel(const float* __restrict__ part,
-                                                                float* __restrict__ dparams) {
-  const int e = blockIdx.x * 256 + threadIdx.x;
-  if (e >= M::K0 * M::S) return;
-  const int om = e / M::S, s = e - om * M::S;
-  const int64_t idx = static_dparam_index<M>(om, s);
-  if (idx < 0) return;
-  float v = 0.f;
-  for (int c = 0; c < M::STATIC_CHUNKS; ++c) v += part[((size_t)c * M::K0 + om) * M::S16 + s];
-  dparams[idx] = v;
 }
 
 // d y0[:, static] = G0[tile]^T (16 x K0) x W0SP (K0 x S16) on MFMA, plus the direct
@@ -3223,14 +3176,6 @@ __device__ __forceinline__ void dy0_static_body(const float* __restrict__ g0buf,
         dy0[((size_t)n * M::R + r) * M::L + 3 + cc] = acc[j][e] + tsum[((4 * g + e) * M::R + r) * M::L + 3 + cc];
     }
   }
-}
-template <class M>
-__global__ __launch_bounds__(256) void ude_dy0_static_kernel(const float* __restrict__ g0buf,
-                                                             const float* __restrict__ pack,
-                                                             const float* __restrict__ dlatent, int n_traj,
-                                                             int n_times, float* __restrict__ dy0) {
-  extern __shared__ float tsum[];
-  dy0_static_body<M>(g0buf, pack, dlatent, n_traj, n_times, dy0, blockIdx.x, tsum);
 }
 
 // ---- the backward's tail in ONE launch ----------------------------------------
@@ -3364,17 +3309,6 @@ __global__ __launch_bounds__(256) void ude_bwd_tail_kernel(const float* __restri
     return;
   }
   if constexpr (M::HOIST) dy0_static_body<M>(g0buf, pack, dlatent, n_traj, n_times, dy0, b - Tail<M>::N_GF, tl);
-}
-
-// fixed-order sum of per-workgroup fp64 partials -> one float (latent_init_loss of the DEC forward)
-template <int V_ = 0>
-__global__ void ude_sum_finalize_kernel(const double* __restrict__ part, int n, float* __restrict__ out) {
-  const int ln = threadIdx.x;
-  double s = 0.0;
-  for (int i = ln; i < n; i += 64) s += part[i];
-#pragma unroll
-  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
-  if (ln == 0) out[0] = (float)s;
 }
 
 template <int V_ = 0>

@@ -300,10 +300,6 @@ struct Model {
   // BAYES: each workgroup slab holds [d mean | d |std|]; the eps stream is laid out
   // per evaluation in this same slab order (SLAB_TOTAL floats per evaluation)
   static constexpr int SLAB_STRIDE = SLAB_TOTAL * (BAYES ? 2 : 1);
-  // static-feature gradient work (outside the main kernel, HOIST only): per-tile
-  // layer-0 row sums G0[tile][K0][16] and split-K partials of dW0[:, static]
-  static constexpr int STATIC_CHUNKS = 128;
-  static constexpr int STATIC_GROUPS = (S16 / 16 + 3) / 4;
 
   static constexpr int ng_before(int w, int d, int k) {
     int s = 0;

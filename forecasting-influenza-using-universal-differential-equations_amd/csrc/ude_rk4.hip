@@ -14,9 +14,11 @@
 using ude::Entry;
 
 namespace {
-// the legacy contiguous statistics vectors ({mean[2], std[2], |Fa|}) as UdeSideStats / UdeSideStatsGrad
-UdeSideStats stats_of(float* stats_out) {
-  UdeSideStats st = {stats_out, stats_out ? stats_out + 2 : nullptr, stats_out ? stats_out + 4 : nullptr, nullptr};
+// the older entries' contiguous statistics vectors ({mean[2], std[2], |Fa|}) as UdeSideStats /
+// UdeSideStatsGrad.  Their forwards promise the fp64 totals in stats_slab[0..4]: sums = stats_slab (the
+// aliasing of workgroup 0's partials is safe: finalize_stats_last, ude_kernels.h)
+UdeSideStats stats_of(float* stats_out, double* sums = nullptr) {
+  UdeSideStats st = {stats_out, stats_out ? stats_out + 2 : nullptr, stats_out ? stats_out + 4 : nullptr, sums};
   return st;
 }
 UdeSideStatsGrad dstats_of(const float* d) {
@@ -69,7 +71,7 @@ int ude_rk4_forward(const UdeModelDesc* m, const UdeProblem* p, const float* pac
   const Entry* e = find(m);
   if (!e) return UDE_E_UNSUPPORTED;
   if (!p || p->n_traj < 1 || p->n_steps < 0 || !stats_out) return UDE_E_INVALID;
-  const UdeSideStats st = stats_of(stats_out);
+  const UdeSideStats st = stats_of(stats_out, stats_slab);
   return e->forward(p, pack, sched, y0, latent, ckpt, stats_slab, &st, nullptr, (hipStream_t)stream);
 }
 
@@ -237,7 +239,7 @@ int ude_rk4_forward_dec(const UdeModelDesc* m, const UdeProblem* p, const float*
   const Entry* e = find(m);
   if (!e) return UDE_E_UNSUPPORTED;
   if (!p || p->n_traj < 1 || p->n_steps < 1 || !stats_out) return UDE_E_INVALID;
-  const UdeSideStats st = stats_of(stats_out);
+  const UdeSideStats st = stats_of(stats_out, stats_slab);
   return e->forward_dec(p, pack, sched, y0, dec_pack, yhat, ckpt, stats_slab, reg_slab, &st, nullptr, reg_out,
                         (hipStream_t)stream);
 }

@@ -36,17 +36,6 @@ UDE_OK, UDE_E_UNSUPPORTED, UDE_E_INVALID, UDE_E_HIP, UDE_E_SOLVER = 0, -1, -2, -
 _ERRS = {UDE_E_UNSUPPORTED: "unsupported model configuration", UDE_E_INVALID: "invalid argument",
          UDE_E_HIP: "HIP runtime error", UDE_E_SOLVER: "adaptive solve failed"}
 
-EXPORTED_SYMBOLS = ("ude_supported", "ude_query", "ude_pack_weights", "ude_pack_weights_bayes",
-                    "ude_rk4_forward", "ude_rk4_backward", "ude_rk4_backward_sir", "ude_dopri5_workspace",
-                    "ude_dopri5_forward", "ude_loss_head_workspace", "ude_loss_head_forward",
-                    "ude_loss_head_backward", "ude_loss_head_backward_sir", "ude_rhs_workspace",
-                    "ude_rhs_forward", "ude_rhs_vjp", "ude_pack_decoder", "ude_rk4_forward_dec",
-                    "ude_decoder_backward", "ude_nll_workspace", "ude_nll_forward", "ude_nll_backward",
-                    "ude_rhs_eval_vjp", "ude_lincomb", "ude_scaled_sumsq", "ude_build_info",
-                    "ude_rk4_forward_ex", "ude_rk4_forward_dec_ex", "ude_rk4_backward_ex", "ude_lincomb_hc",
-                    "ude_dopri_ratio", "ude_rk4_forecast_dec", "ude_forecast_summary_workspace",
-                    "ude_forecast_summary", "ude_forecast_verify_workspace", "ude_forecast_verify",
-                    "ude_rk4_forecast_dyn")
 SUMSQ_WS = 1025          # doubles of ude_scaled_sumsq's output / workspace (UDE_SUMSQ_WS)
 
 
@@ -116,164 +105,134 @@ def check(rc: int, what: str) -> None:
         raise UdeError(f"{what} failed: {_ERRS.get(rc, rc)} (code {rc})")
 
 
+_vp, _i32, _i64, _f32, _f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_float, ctypes.c_double
+_pd, _pp, _pvp, _pi64 = ctypes.POINTER(UdeModelDesc), ctypes.POINTER(UdeProblem), ctypes.POINTER(_vp), ctypes.POINTER(_i64)
+_pst, _pdst = ctypes.POINTER(UdeSideStats), ctypes.POINTER(UdeSideStatsGrad)
+
+
+def _sig(method: Optional[str], *groups) -> tuple:
+    """(NativeLib method generated for the function or None, its argument types); a group is one type or
+    (count, type)."""
+    types: List[object] = []
+    for g in groups:
+        types += [g[1]] * g[0] if isinstance(g, tuple) else [g]
+    return method, tuple(types)
+
+
+# The binding's one table: every function of include/ude_rk4.h -> its argument types, in the header's
+# order.  Each returns int (an UDE_E_* code) except ude_build_info.  A function with a method name gets
+# the method NativeLib.<name>(*args) = check(function(*args)); the others have a hand-written method that
+# does more.  A ctypes Structure (or c_int64) passed where the table says POINTER(T) goes by reference.
+_CABI: Dict[str, tuple] = {
+    "ude_supported": _sig(None, _pd),
+    "ude_query": _sig(None, _pd, _pp, _i32, ctypes.POINTER(UdeSizes)),
+    "ude_pack_weights": _sig(None, _pd, _pvp, _pvp, (2, _vp)),
+    "ude_pack_weights_bayes": _sig(None, _pd, _pp, (4, _pvp), (3, _vp)),
+    "ude_rk4_forward": _sig("forward", _pd, _pp, (8, _vp)),
+    "ude_rk4_backward": _sig("backward", _pd, _pp, (11, _vp)),
+    "ude_rk4_backward_sir": _sig("backward_sir", _pd, _pp, (12, _vp)),
+    "ude_rk4_forward_ex": _sig("forward_ex", _pd, _pp, (7, _vp), _pst, _vp),
+    "ude_rk4_forward_dec_ex": _sig("forward_dec_ex", _pd, _pp, (9, _vp), _pst, (2, _vp)),
+    "ude_rk4_backward_ex": _sig("backward_ex", _pd, _pp, (6, _vp), _pst, _pdst, (5, _vp)),
+    "ude_dopri5_workspace": _sig(None, _pd, _pp, _i32, _pi64),
+    "ude_dopri5_forward": _sig(None, _pd, _pp, (2, _vp), (3, _f64), _i32, (4, _vp), ctypes.POINTER(UdeDopriInfo), _vp),
+    "ude_loss_head_workspace": _sig(None, _pd, (4, _i32), _pi64),
+    "ude_loss_head_forward": _sig("loss_forward", _pd, (3, _i32), (7, _vp)),
+    "ude_loss_head_backward": _sig("loss_backward", _pd, (3, _i32), (10, _vp)),
+    "ude_loss_head_backward_sir": _sig("loss_backward_sir", _pd, (3, _i32), (10, _vp)),
+    "ude_rhs_workspace": _sig(None, _pd, _pp, _i32, _pi64),
+    "ude_rhs_forward": _sig("rhs_forward", _pd, _pp, (6, _vp)),
+    "ude_rhs_vjp": _sig("rhs_vjp", _pd, _pp, (9, _vp)),
+    "ude_pack_decoder": _sig("pack_decoder", _pd, (4, _vp)),
+    "ude_rk4_forward_dec": _sig("forward_dec", _pd, _pp, (11, _vp)),
+    "ude_decoder_backward": _sig("decoder_backward", _pd, _pp, (10, _vp)),
+    "ude_nll_workspace": _sig(None, _pd, (3, _i32), _pi64),
+    "ude_nll_forward": _sig("nll_forward", _pd, (3, _i32), (5, _vp)),
+    "ude_nll_backward": _sig("nll_backward", _pd, (3, _i32), (6, _vp)),
+    "ude_rhs_eval_vjp": _sig("rhs_eval_vjp", _pd, _pp, (4, _vp), _f32, (4, _vp)),
+    "ude_lincomb": _sig(None, _i64, _vp, _pvp, _i32, (3, _vp)),
+    "ude_scaled_sumsq": _sig("scaled_sumsq", _i64, (3, _vp), (2, _f64), (2, _vp)),
+    "ude_lincomb_hc": _sig(None, _i64, _vp, _pvp, _i32, ctypes.POINTER(_f32), (2, _vp)),
+    "ude_dopri_ratio": _sig(None, (3, _vp), (2, _f64), _vp, _pi64, _i32, _vp, _i32, _f64, (3, _vp)),
+    "ude_rk4_forecast_dec": _sig("forecast_dec", _pd, _pp, (7, _vp), _pst, _vp),
+    "ude_rk4_forecast_dyn": _sig("forecast_dyn", _pd, _pp, (8, _vp), _pst, _vp),
+    "ude_forecast_summary_workspace": _sig(None, (5, _i32), _pi64),
+    "ude_forecast_summary": _sig("forecast_summary", (4, _i32), (4, _vp), _i32, (6, _vp)),
+    "ude_forecast_verify_workspace": _sig(None, (7, _i32), _pi64),
+    "ude_forecast_verify": _sig("forecast_verify", (4, _i32), (4, _vp), _i32, _vp, (2, _i32), (8, _vp)),
+    "ude_build_info": _sig(None),
+}
+EXPORTED_SYMBOLS = tuple(_CABI)
+# integer / float arguments accept whatever int() / float() accept (numpy and torch scalars)
+_CONV = {_i32: int, _i64: int, _f32: float, _f64: float}
+
+
+def _converting(fn, types):
+    """fn with the table's integer / float positions converted; fn itself when there are none.  Resolved once
+    per function, so a call costs no more than the ctypes call and its conversions."""
+    conv = tuple((i, _CONV[t]) for i, t in enumerate(types) if t in _CONV)
+    if not conv:
+        return fn
+
+    def call(*args):
+        args = list(args)
+        for i, c in conv:
+            args[i] = c(args[i])
+        return fn(*args)
+    return call
+
+
 class NativeLib:
-    """ctypes view of one libude_rk4*.so."""
+    """ctypes view of one libude_rk4*.so: the methods generated from ``_CABI`` (below the class: forward,
+    backward_ex, ...) and the hand-written ones."""
 
     def __init__(self, path: str):
         self.path = path
         self.lib = ctypes.CDLL(path)
-        L = self.lib
-        vp, i32 = ctypes.c_void_p, ctypes.c_int
-        pdesc, pprob = ctypes.POINTER(UdeModelDesc), ctypes.POINTER(UdeProblem)
-        L.ude_supported.argtypes = [pdesc]
-        L.ude_supported.restype = i32
-        L.ude_query.argtypes = [pdesc, pprob, i32, ctypes.POINTER(UdeSizes)]
-        L.ude_query.restype = i32
-        L.ude_pack_weights.argtypes = [pdesc, ctypes.POINTER(vp), ctypes.POINTER(vp), vp, vp]
-        L.ude_pack_weights.restype = i32
-        pvp = ctypes.POINTER(vp)
-        L.ude_pack_weights_bayes.argtypes = [pdesc, pprob, pvp, pvp, pvp, pvp, vp, vp, vp]
-        L.ude_pack_weights_bayes.restype = i32
-        L.ude_rk4_forward.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_rk4_forward.restype = i32
-        L.ude_rk4_backward.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_rk4_backward.restype = i32
-        L.ude_rk4_backward_sir.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_rk4_backward_sir.restype = i32
-        L.ude_dopri5_workspace.argtypes = [pdesc, pprob, i32, ctypes.POINTER(ctypes.c_int64)]
-        L.ude_dopri5_workspace.restype = i32
-        dbl = ctypes.c_double
-        L.ude_dopri5_forward.argtypes = [pdesc, pprob, vp, vp, dbl, dbl, dbl, ctypes.c_int32, vp, vp, vp, vp,
-                                         ctypes.POINTER(UdeDopriInfo), vp]
-        L.ude_dopri5_forward.restype = i32
-        L.ude_loss_head_workspace.argtypes = [pdesc, i32, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-        L.ude_loss_head_workspace.restype = i32
-        L.ude_loss_head_forward.argtypes = [pdesc, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_loss_head_forward.restype = i32
-        L.ude_loss_head_backward.argtypes = [pdesc, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_loss_head_backward.restype = i32
-        L.ude_loss_head_backward_sir.argtypes = [pdesc, i32, i32, i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_loss_head_backward_sir.restype = i32
-        L.ude_rhs_workspace.argtypes = [pdesc, pprob, i32, ctypes.POINTER(ctypes.c_int64)]
-        L.ude_rhs_workspace.restype = i32
-        L.ude_rhs_forward.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp]
-        L.ude_rhs_forward.restype = i32
-        L.ude_rhs_vjp.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_rhs_vjp.restype = i32
-        L.ude_pack_decoder.argtypes = [pdesc, vp, vp, vp, vp]
-        L.ude_pack_decoder.restype = i32
-        L.ude_rk4_forward_dec.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_rk4_forward_dec.restype = i32
-        L.ude_decoder_backward.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp, vp]
-        L.ude_decoder_backward.restype = i32
-        L.ude_nll_workspace.argtypes = [pdesc, i32, i32, i32, ctypes.POINTER(ctypes.c_int64)]
-        L.ude_nll_workspace.restype = i32
-        L.ude_nll_forward.argtypes = [pdesc, i32, i32, i32, vp, vp, vp, vp, vp]
-        L.ude_nll_forward.restype = i32
-        L.ude_nll_backward.argtypes = [pdesc, i32, i32, i32, vp, vp, vp, vp, vp, vp]
-        L.ude_nll_backward.restype = i32
-        L.ude_rhs_eval_vjp.argtypes = [pdesc, pprob, vp, vp, vp, vp, ctypes.c_float, vp, vp, vp, vp]
-        L.ude_rhs_eval_vjp.restype = i32
-        L.ude_lincomb.argtypes = [ctypes.c_int64, vp, pvp, ctypes.c_int32, vp, vp, vp]
-        L.ude_lincomb.restype = i32
-        L.ude_scaled_sumsq.argtypes = [ctypes.c_int64, vp, vp, vp, dbl, dbl, vp, vp]
-        L.ude_scaled_sumsq.restype = i32
-        L.ude_lincomb_hc.argtypes = [ctypes.c_int64, vp, pvp, ctypes.c_int32, ctypes.POINTER(ctypes.c_float), vp, vp]
-        L.ude_lincomb_hc.restype = i32
-        L.ude_dopri_ratio.argtypes = [vp, vp, vp, dbl, dbl, vp, ctypes.POINTER(ctypes.c_int64), ctypes.c_int32, vp,
-                                      ctypes.c_int32, dbl, vp, vp, vp]
-        L.ude_dopri_ratio.restype = i32
-        L.ude_build_info.argtypes = []
-        L.ude_build_info.restype = ctypes.c_char_p
-        pst, pdst = ctypes.POINTER(UdeSideStats), ctypes.POINTER(UdeSideStatsGrad)
-        L.ude_rk4_forward_ex.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, pst, vp]
-        L.ude_rk4_forward_ex.restype = i32
-        L.ude_rk4_forward_dec_ex.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, vp, pst, vp, vp]
-        L.ude_rk4_forward_dec_ex.restype = i32
-        L.ude_rk4_backward_ex.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, pst, pdst, vp, vp, vp, vp, vp]
-        L.ude_rk4_backward_ex.restype = i32
-        L.ude_rk4_forecast_dec.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, pst, vp]
-        L.ude_rk4_forecast_dec.restype = i32
-        L.ude_rk4_forecast_dyn.argtypes = [pdesc, pprob, vp, vp, vp, vp, vp, vp, vp, vp, pst, vp]
-        L.ude_rk4_forecast_dyn.restype = i32
-        i32s = ctypes.c_int32
-        L.ude_forecast_summary_workspace.argtypes = [i32s, i32s, i32s, i32s, i32s, ctypes.POINTER(ctypes.c_int64)]
-        L.ude_forecast_summary_workspace.restype = i32
-        L.ude_forecast_summary.argtypes = [i32s, i32s, i32s, i32s, vp, vp, vp, vp, i32s, vp, vp, vp, vp, vp, vp]
-        L.ude_forecast_summary.restype = i32
-        L.ude_forecast_verify_workspace.argtypes = [i32s, i32s, i32s, i32s, i32s, i32s, i32s,
-                                                    ctypes.POINTER(ctypes.c_int64)]
-        L.ude_forecast_verify_workspace.restype = i32
-        L.ude_forecast_verify.argtypes = [i32s, i32s, i32s, i32s, vp, vp, vp, vp, i32s, vp, i32s, i32s, vp, vp, vp, vp,
-                                          vp, vp, vp, vp]
-        L.ude_forecast_verify.restype = i32
+        self._raw = {}
+        for cname, (name, types) in _CABI.items():
+            fn = getattr(self.lib, cname)
+            fn.argtypes = list(types)
+            fn.restype = ctypes.c_char_p if cname == "ude_build_info" else ctypes.c_int
+            self._raw[cname] = _converting(fn, types)
+
+    def _rc(self, cname: str, *args) -> int:
+        return self._raw[cname](*args)
+
+    def _call(self, cname: str, *args) -> None:
+        check(self._raw[cname](*args), cname)
+
+    def _workspace(self, cname: str, *args) -> int:
+        out = ctypes.c_int64(0)
+        self._call(cname, *args, out)
+        return int(out.value)
 
     def supported(self, desc: UdeModelDesc) -> bool:
-        return bool(self.lib.ude_supported(ctypes.byref(desc)))
+        return bool(self._rc("ude_supported", desc))
 
     def query(self, desc, prob, device: int) -> UdeSizes:
         out = UdeSizes()
-        check(self.lib.ude_query(ctypes.byref(desc), ctypes.byref(prob), int(device), ctypes.byref(out)), "ude_query")
+        self._call("ude_query", desc, prob, device, out)
         return out
 
     def pack(self, desc, w_ptrs: Sequence[int], b_ptrs: Sequence[int], pack_ptr: int, stream: int) -> None:
-        n = len(w_ptrs)
-        W = (ctypes.c_void_p * n)(*w_ptrs)
-        B = (ctypes.c_void_p * n)(*b_ptrs)
-        check(self.lib.ude_pack_weights(ctypes.byref(desc), W, B, pack_ptr, stream), "ude_pack_weights")
+        arr = lambda ptrs: (ctypes.c_void_p * len(w_ptrs))(*ptrs)
+        self._call("ude_pack_weights", desc, arr(w_ptrs), arr(b_ptrs), pack_ptr, stream)
 
     def pack_bayes(self, desc, prob, w_mean: Sequence[int], b_mean: Sequence[int], w_std: Sequence[int],
                    b_std: Sequence[int], eps_ptr: int, pack_ptr: int, stream: int) -> None:
-        n = len(w_mean)
-        arr = lambda ptrs: (ctypes.c_void_p * n)(*ptrs)
-        check(self.lib.ude_pack_weights_bayes(ctypes.byref(desc), ctypes.byref(prob), arr(w_mean), arr(b_mean),
-                                              arr(w_std), arr(b_std), eps_ptr, pack_ptr, stream),
-              "ude_pack_weights_bayes")
-
-    def forward(self, desc, prob, pack, sched, y0, latent, ckpt, stats_slab, stats_out, stream) -> None:
-        check(self.lib.ude_rk4_forward(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, latent, ckpt,
-                                       stats_slab, stats_out, stream), "ude_rk4_forward")
-
-    def backward(self, desc, prob, pack, sched, y0, ckpt, dlatent, stats_out, dstats, dy0, slab, dparams,
-                 stream) -> None:
-        check(self.lib.ude_rk4_backward(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, ckpt, dlatent,
-                                        stats_out, dstats, dy0, slab, dparams, stream), "ude_rk4_backward")
-
-    def backward_sir(self, desc, prob, pack, sched, y0, ckpt, dlatent, dlat_sir, stats_out, dstats, dy0, slab,
-                     dparams, stream) -> None:
-        check(self.lib.ude_rk4_backward_sir(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, ckpt, dlatent,
-                                            dlat_sir, stats_out, dstats, dy0, slab, dparams, stream),
-              "ude_rk4_backward_sir")
-
-    def forward_ex(self, desc, prob, pack, sched, y0, latent, ckpt, stats_slab, ctl, stats: UdeSideStats,
-                   stream) -> None:
-        check(self.lib.ude_rk4_forward_ex(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, latent, ckpt,
-                                          stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forward_ex")
-
-    def forward_dec_ex(self, desc, prob, pack, sched, y0, dec_pack, yhat, ckpt, stats_slab, reg_slab, ctl,
-                       stats: UdeSideStats, reg_out, stream) -> None:
-        check(self.lib.ude_rk4_forward_dec_ex(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack,
-                                              yhat, ckpt, stats_slab, reg_slab, ctl, ctypes.byref(stats), reg_out,
-                                              stream), "ude_rk4_forward_dec_ex")
-
-    def backward_ex(self, desc, prob, pack, sched, y0, ckpt, dlatent, dlat_sir, stats: UdeSideStats,
-                    dstats: UdeSideStatsGrad, dy0, slab, ctl, dparams, stream) -> None:
-        check(self.lib.ude_rk4_backward_ex(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, ckpt, dlatent,
-                                           dlat_sir, ctypes.byref(stats), ctypes.byref(dstats), dy0, slab, ctl,
-                                           dparams, stream), "ude_rk4_backward_ex")
+        arr = lambda ptrs: (ctypes.c_void_p * len(w_mean))(*ptrs)
+        self._call("ude_pack_weights_bayes", desc, prob, arr(w_mean), arr(b_mean), arr(w_std), arr(b_std), eps_ptr,
+                   pack_ptr, stream)
 
     def dopri5_workspace(self, desc, prob, device: int) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_dopri5_workspace(ctypes.byref(desc), ctypes.byref(prob), int(device), ctypes.byref(out)),
-              "ude_dopri5_workspace")
-        return int(out.value)
+        return self._workspace("ude_dopri5_workspace", desc, prob, device)
 
     def dopri5_forward(self, desc, prob, pack, t_out, rtol, atol, first_step, max_steps, y0, latent, ws,
                        stats_out, stream) -> UdeDopriInfo:
         info = UdeDopriInfo()
-        rc = self.lib.ude_dopri5_forward(ctypes.byref(desc), ctypes.byref(prob), pack, t_out, float(rtol),
-                                         float(atol), float(first_step), int(max_steps), y0, latent, ws, stats_out,
-                                         ctypes.byref(info), stream)
+        rc = self._rc("ude_dopri5_forward", desc, prob, pack, t_out, rtol, atol, first_step, max_steps, y0, latent,
+                      ws, stats_out, info, stream)
         if rc == UDE_E_SOLVER:
             why = {1: "underflow in dt", 2: "max_num_steps exceeded", 3: "non-finite values in state `y`"}
             raise AssertionError(f"dopri5: {why.get(info.status, info.status)} "
@@ -282,122 +241,55 @@ class NativeLib:
         return info
 
     def loss_workspace(self, desc, T, S, B, device) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_loss_head_workspace(ctypes.byref(desc), int(T), int(S), int(B), int(device),
-                                               ctypes.byref(out)), "ude_loss_head_workspace")
-        return int(out.value)
-
-    def loss_forward(self, desc, T, S, B, latent, W, b, y, ws, out, stream) -> None:
-        check(self.lib.ude_loss_head_forward(ctypes.byref(desc), int(T), int(S), int(B), latent, W, b, y, ws, out,
-                                             stream), "ude_loss_head_forward")
-
-    def loss_backward(self, desc, T, S, B, latent, W, b, y, grad, ws, dlat, dW, db, stream) -> None:
-        check(self.lib.ude_loss_head_backward(ctypes.byref(desc), int(T), int(S), int(B), latent, W, b, y, grad,
-                                              ws, dlat, dW, db, stream), "ude_loss_head_backward")
-
-    def loss_backward_sir(self, desc, T, S, B, latent, W, b, y, grad, ws, dlat_sir, dW, db, stream) -> None:
-        check(self.lib.ude_loss_head_backward_sir(ctypes.byref(desc), int(T), int(S), int(B), latent, W, b, y, grad,
-                                                  ws, dlat_sir, dW, db, stream), "ude_loss_head_backward_sir")
+        return self._workspace("ude_loss_head_workspace", desc, T, S, B, device)
 
     def rhs_workspace(self, desc, prob, device: int) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_rhs_workspace(ctypes.byref(desc), ctypes.byref(prob), int(device), ctypes.byref(out)),
-              "ude_rhs_workspace")
-        return int(out.value)
+        return self._workspace("ude_rhs_workspace", desc, prob, device)
 
-    def rhs_forward(self, desc, prob, pack, x, f, rates, fa, stream) -> None:
-        check(self.lib.ude_rhs_forward(ctypes.byref(desc), ctypes.byref(prob), pack, x, f, rates, fa, stream),
-              "ude_rhs_forward")
+    def nll_workspace(self, desc, T, S, B) -> int:
+        return self._workspace("ude_nll_workspace", desc, T, S, B)
 
-    def rhs_vjp(self, desc, prob, pack, x, cot_f, cot_rates, cot_fa, dx, ws, dparams, stream) -> None:
-        check(self.lib.ude_rhs_vjp(ctypes.byref(desc), ctypes.byref(prob), pack, x, cot_f, cot_rates, cot_fa, dx,
-                                   ws, dparams, stream), "ude_rhs_vjp")
+    def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
+        return self._workspace("ude_forecast_summary_workspace", T, S, B, R, n_q)
 
-    def rhs_eval_vjp(self, desc, prob, pack, x, cot_f, f_out, f_scale, dx, ws, dparams, stream) -> None:
-        check(self.lib.ude_rhs_eval_vjp(ctypes.byref(desc), ctypes.byref(prob), pack, x, cot_f, f_out,
-                                        float(f_scale), dx, ws, dparams, stream), "ude_rhs_eval_vjp")
+    def forecast_verify_workspace(self, T, S, B, R, n_q, n_alpha, n_pit) -> int:
+        return self._workspace("ude_forecast_verify_workspace", T, S, B, R, n_q, n_alpha, n_pit)
 
     def lincomb(self, n, base, ks: Sequence[int], coef, out, stream) -> None:
         arr = (ctypes.c_void_p * len(ks))(*ks)
-        check(self.lib.ude_lincomb(int(n), base, arr, len(ks), coef, out, stream), "ude_lincomb")
+        self._call("ude_lincomb", n, base, arr, len(ks), coef, out, stream)
 
     def lincomb_hc(self, n, base, ks: Sequence[int], coef: Sequence[float], out, stream) -> None:
         """ude_lincomb with host coefficients (fp32 values, copied into the launch)."""
         arr = (ctypes.c_void_p * len(ks))(*ks)
         cv = (ctypes.c_float * len(coef))(*coef)
-        check(self.lib.ude_lincomb_hc(int(n), base, arr, len(ks), cv, out, stream), "ude_lincomb_hc")
+        self._call("ude_lincomb_hc", n, base, arr, len(ks), cv, out, stream)
 
     def dopri_ratio(self, err, y0, y1, atol, rtol, ssq, ns: Sequence[int], extra, n_extra, dt, flag, status,
                     stream) -> None:
         na = (ctypes.c_int64 * max(len(ns), 1))(*ns)
-        check(self.lib.ude_dopri_ratio(err, y0, y1, float(atol), float(rtol), ssq, na, len(ns), extra, int(n_extra),
-                                       float(dt), flag, status, stream), "ude_dopri_ratio")
-
-    def scaled_sumsq(self, n, err, y0, y1, atol, rtol, out, stream) -> None:
-        check(self.lib.ude_scaled_sumsq(int(n), err, y0, y1, float(atol), float(rtol), out, stream),
-              "ude_scaled_sumsq")
-
-    def pack_decoder(self, desc, W, b, out, stream) -> None:
-        check(self.lib.ude_pack_decoder(ctypes.byref(desc), W, b, out, stream), "ude_pack_decoder")
-
-    def forward_dec(self, desc, prob, pack, sched, y0, dec_pack, yhat, ckpt, stats_slab, reg_slab, stats_out,
-                    reg_out, stream) -> None:
-        check(self.lib.ude_rk4_forward_dec(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
-                                           ckpt, stats_slab, reg_slab, stats_out, reg_out, stream),
-              "ude_rk4_forward_dec")
-
-    def decoder_backward(self, desc, prob, sched, ckpt, dyhat, W, grad_reg, ws, dl3, dW, db, stream) -> None:
-        check(self.lib.ude_decoder_backward(ctypes.byref(desc), ctypes.byref(prob), sched, ckpt, dyhat, W, grad_reg,
-                                            ws, dl3, dW, db, stream), "ude_decoder_backward")
-
-    def nll_workspace(self, desc, T, S, B) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_nll_workspace(ctypes.byref(desc), int(T), int(S), int(B), ctypes.byref(out)),
-              "ude_nll_workspace")
-        return int(out.value)
-
-    def nll_forward(self, desc, T, S, B, yhat, y, ws, out, stream) -> None:
-        check(self.lib.ude_nll_forward(ctypes.byref(desc), int(T), int(S), int(B), yhat, y, ws, out, stream),
-              "ude_nll_forward")
-
-    def nll_backward(self, desc, T, S, B, yhat, y, grad, ws, dyhat, stream) -> None:
-        check(self.lib.ude_nll_backward(ctypes.byref(desc), int(T), int(S), int(B), yhat, y, grad, ws, dyhat,
-                                        stream), "ude_nll_backward")
-
-    def forecast_dec(self, desc, prob, pack, sched, y0, dec_pack, yhat, stats_slab, ctl, stats: UdeSideStats,
-                     stream) -> None:
-        check(self.lib.ude_rk4_forecast_dec(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
-                                            stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forecast_dec")
-
-    def forecast_dyn(self, desc, prob, pack, sched, y0, dec_pack, yhat, dyn, stats_slab, ctl, stats: UdeSideStats,
-                     stream) -> None:
-        check(self.lib.ude_rk4_forecast_dyn(ctypes.byref(desc), ctypes.byref(prob), pack, sched, y0, dec_pack, yhat,
-                                            dyn, stats_slab, ctl, ctypes.byref(stats), stream), "ude_rk4_forecast_dyn")
-
-    def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_forecast_summary_workspace(int(T), int(S), int(B), int(R), int(n_q), ctypes.byref(out)),
-              "ude_forecast_summary_workspace")
-        return int(out.value)
-
-    def forecast_summary(self, T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, scores, stream) -> None:
-        check(self.lib.ude_forecast_summary(int(T), int(S), int(B), int(R), yhat, scale, y_true, q, int(n_q), ws,
-                                            mean, std, quant, scores, stream), "ude_forecast_summary")
-
-    def forecast_verify_workspace(self, T, S, B, R, n_q, n_alpha, n_pit) -> int:
-        out = ctypes.c_int64(0)
-        check(self.lib.ude_forecast_verify_workspace(int(T), int(S), int(B), int(R), int(n_q), int(n_alpha),
-                                                     int(n_pit), ctypes.byref(out)), "ude_forecast_verify_workspace")
-        return int(out.value)
-
-    def forecast_verify(self, T, S, B, R, yhat, scale, y_true, q, n_q, alpha, n_alpha, n_pit, ws, mean, std, quant,
-                        scores, day, region, stream) -> None:
-        check(self.lib.ude_forecast_verify(int(T), int(S), int(B), int(R), yhat, scale, y_true, q, int(n_q), alpha,
-                                           int(n_alpha), int(n_pit), ws, mean, std, quant, scores, day, region,
-                                           stream), "ude_forecast_verify")
+        self._call("ude_dopri_ratio", err, y0, y1, atol, rtol, ssq, na, len(ns), extra, n_extra, dt, flag, status,
+                   stream)
 
     def build_info(self) -> str:
         return self.lib.ude_build_info().decode()
+
+
+def _method(cname: str, name: str, n_args: int):
+    def method(self, *args) -> None:
+        if len(args) != n_args:
+            raise TypeError(f"{name} takes {n_args} arguments ({len(args)} given)")
+        rc = self._raw[cname](*args)
+        if rc != UDE_OK:
+            check(rc, cname)
+    method.__name__ = name
+    method.__doc__ = f"check({cname}(*args)): the arguments of include/ude_rk4.h, in its order."
+    return method
+
+
+for _cname, (_name, _types) in _CABI.items():
+    if _name:
+        setattr(NativeLib, _name, _method(_cname, _name, len(_types)))
 
 
 # ---------------------------------------------------------------------------

@@ -389,13 +389,12 @@ def _forecast_plan(ode, y0, t, step_size):
     return plan
 
 
-def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear) -> Optional[torch.Tensor]:
-    """y_hat (T, N, R) = Decoder(odeint(ode, y0, t)[..., :3]) of the inference solve
-    (ude_rk4_forecast_dec: no autograd, no latent, no checkpoint), or None when the decoder epilogue
-    does not apply (``decoder_head.eligible``) or an output time is not a grid point.  Records the
-    solve's side statistics on ``ode`` as every fused solve does (``posterior()``, the tracker)."""
-    if not decoder_head.eligible(ode, y0, linear):
-        return None
+def _solve_decode(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear, n_dyn: int = 0,
+                  out: Optional[torch.Tensor] = None) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+    """The inference solve with the decoder epilogue behind ``solve_decode_forecast`` (``n_dyn`` = 0:
+    ude_rk4_forecast_dec) and ``solve_decode_dynamics`` (``n_dyn`` channels into ``out`` or a new tensor:
+    ude_rk4_forecast_dyn): ``(y_hat, dyn or None)``, or None when an output time is not a grid point.
+    Records the solve's side statistics on ``ode``."""
     with torch.no_grad(), torch.cuda.device(y0.device):
         plan = _forecast_plan(ode, y0, t, step_size)
         if plan.out_k is None:
@@ -404,7 +403,7 @@ def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
         stream = _fused._stream(dev)
         sz = plan.sizes
         y0 = y0.detach().contiguous()
-        if ode.uncertainty == "bayes":
+        if getattr(ode, "uncertainty", "none") == "bayes":
             mus, sds = ode.ude_mean_std()
             eps = ode.take_eps(4 * plan.prob.n_steps, sum(int(p.numel()) for p in mus), dev)
             pack = _fused._bayes_pack(plan, mus, sds, eps, dev)
@@ -418,14 +417,39 @@ def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
         plan.lib.pack_decoder(plan.desc, Wd.data_ptr(), bd.data_ptr(), dec_pack.data_ptr(), stream)
         N, R, L = y0.shape
         yhat = torch.empty((plan.n_times, N, R), dtype=torch.float32, device=dev)
+        dyn = None
+        if n_dyn:
+            shape = (n_dyn, plan.n_times, N, R)
+            if out is None:
+                dyn = torch.empty(shape, dtype=torch.float32, device=dev)
+            else:
+                if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
+                    raise ValueError(f"solve_decode_dynamics: out must be a contiguous fp32 {shape} tensor on {dev}")
+                dyn = out
         stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
         stats, sums, st = _fused._stats_out(plan, dev)
-        with _fused._timed("forecast_dec"):
-            plan.lib.forecast_dec(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                                  dec_pack.data_ptr(), yhat.data_ptr(), stats_slab.data_ptr(),
-                                  _fused._ctl(plan, dev).data_ptr(), st, stream)
+        head = (plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(), dec_pack.data_ptr(),
+                yhat.data_ptr())
+        tail = (stats_slab.data_ptr(), _fused._ctl(plan, dev).data_ptr(), st, stream)
+        if dyn is None:
+            with _fused._timed("forecast_dec"):
+                plan.lib.forecast_dec(*head, *tail)
+        else:
+            with _fused._timed("forecast_dyn"):
+                plan.lib.forecast_dyn(*head, dyn.data_ptr(), *tail)
         ode._record_fused(stats, plan.n_eval, sums=sums)
-    return yhat
+    return yhat, dyn
+
+
+def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear) -> Optional[torch.Tensor]:
+    """y_hat (T, N, R) = Decoder(odeint(ode, y0, t)[..., :3]) of the inference solve
+    (ude_rk4_forecast_dec: no autograd, no latent, no checkpoint), or None when the decoder epilogue
+    does not apply (``decoder_head.eligible``) or an output time is not a grid point.  Records the
+    solve's side statistics on ``ode`` as every fused solve does (``posterior()``, the tracker)."""
+    if not decoder_head.eligible(ode, y0, linear):
+        return None
+    res = _solve_decode(ode, y0, t, step_size, linear)
+    return None if res is None else res[0]
 
 
 def solve_decode_dynamics(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear,
@@ -441,39 +465,9 @@ def solve_decode_dynamics(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
     (C, T, N, R) tensor on y0's device to receive ``dyn`` (exactly its C * T * N * R floats are written)."""
     if getattr(ode, "uncertainty", "none") == "bayes" or not decoder_head.eligible(ode, y0, linear):
         return None
-    with torch.no_grad(), torch.cuda.device(y0.device):
-        plan = _forecast_plan(ode, y0, t, step_size)
-        if plan.out_k is None:
-            return None
-        dev = y0.device
-        stream = _fused._stream(dev)
-        sz = plan.sizes
-        y0 = y0.detach().contiguous()
-        params = []
-        for lin in ode.ude_linears():
-            params += [lin.weight, lin.bias]
-        pack = _fused.packed_weights(plan, params, dev)
-        Wd, bd = linear.weight.detach().contiguous(), linear.bias.detach().contiguous()
-        dec_pack = torch.empty(sz.dec_pack_bytes // 4, dtype=torch.float32, device=dev)
-        plan.lib.pack_decoder(plan.desc, Wd.data_ptr(), bd.data_ptr(), dec_pack.data_ptr(), stream)
-        N, R, L = y0.shape
-        names = dynamics_names(ode)
-        yhat = torch.empty((plan.n_times, N, R), dtype=torch.float32, device=dev)
-        shape = (len(names), plan.n_times, N, R)
-        if out is None:
-            dyn = torch.empty(shape, dtype=torch.float32, device=dev)
-        else:
-            if tuple(out.shape) != shape or out.dtype != torch.float32 or out.device != dev or not out.is_contiguous():
-                raise ValueError(f"solve_decode_dynamics: out must be a contiguous fp32 {shape} tensor on {dev}")
-            dyn = out
-        stats_slab = torch.empty(max(sz.stats_slab_bytes // 8, 1), dtype=torch.float64, device=dev)
-        stats, sums, st = _fused._stats_out(plan, dev)
-        with _fused._timed("forecast_dyn"):
-            plan.lib.forecast_dyn(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(),
-                                  dec_pack.data_ptr(), yhat.data_ptr(), dyn.data_ptr(), stats_slab.data_ptr(),
-                                  _fused._ctl(plan, dev).data_ptr(), st, stream)
-        ode._record_fused(stats, plan.n_eval, sums=sums)
-    return yhat, dyn, names
+    names = dynamics_names(ode)
+    res = _solve_decode(ode, y0, t, step_size, linear, len(names), out)
+    return None if res is None else (*res, names)
 
 
 def _mean_stack(stack, h: torch.Tensor) -> torch.Tensor:

@@ -88,7 +88,9 @@ typedef struct UdeSizes {
   int64_t dec_ws_bytes;     /* ude_decoder_backward workspace                     */
   int64_t act_bytes;        /* part of ckpt_bytes holding stored activation rows
                                (0 with UdeProblem.recompute = 1)                 */
-  int64_t ctl_bytes;        /* control words of the *_ex calls (see below)         */
+  int64_t ctl_bytes;        /* control words of the *_ex calls (see below); stats_slab and, where the
+                               backward has a tail kernel, grad_slab end in as many spare ones: a
+                               call handed none zeroes and uses those                              */
 } UdeSizes;
 
 /*
@@ -170,16 +172,14 @@ int ude_rk4_backward_sir(const UdeModelDesc* m, const UdeProblem* p, const float
  * hands over as three outputs / three cotangents: no split, concatenation or zero-fill between the
  * solve and the loss), and finalise in the solve's own launches:
  *   ude_rk4_forward_ex / ude_rk4_forward_dec_ex: the last workgroup of the forward kernel turns the
- *     per-workgroup fp64 partials (stats_slab) into mean / std / |Fa| (and reg_out), in the fixed
- *     order of the separate finalize kernel of ude_rk4_forward (same bits);
+ *     per-workgroup fp64 partials (stats_slab) into mean / std / |Fa| (and reg_out), in a fixed order;
  *   ude_rk4_backward_ex: the per-workgroup gradient slabs, the static-feature weight gradient and
- *     dy0's static dims are formed by ONE trailing kernel (instead of four).
+ *     dy0's static dims are formed by ONE trailing kernel.
  * ctl: ude_query's ctl_bytes of device memory, zeroed by the caller ONCE (e.g. at allocation) and
  * left zero by every call; calls that share a ctl buffer must be stream ordered (one ctl per stream
  * that runs solves concurrently).  Any UdeSideStats pointer of an absent net may be NULL; every
- * UdeSideStatsGrad pointer is nullable (zero cotangent).  Results equal ude_rk4_forward /
- * ude_rk4_backward_sir (statistics bitwise; the static-feature weight gradient within fp32 summation
- * order). */
+ * UdeSideStatsGrad pointer is nullable (zero cotangent).  ude_rk4_forward / _forward_dec / _backward /
+ * _backward_sir are these launches behind a memset of spare control words: the same bits in every result. */
 typedef struct UdeSideStats {
   float* mean;      /* 2 floats: mean beta, mean gamma        (posterior().loc)   */
   float* std;       /* 2 floats: unbiased std of beta, gamma  (posterior().scale) */
@@ -362,7 +362,7 @@ int ude_dopri_ratio(const float* err, const float* y0, const float* y1, double a
  * Decoder(latent[..., :3]) at every output time and the side statistics; no latent, no checkpoint, no
  * stored activations, no final-state block and no latent_init_loss.  Preconditions of
  * ude_rk4_forward_dec_ex (every output time a grid point, n_steps >= 1; UDE_E_INVALID otherwise);
- * pack / dec_pack / sched / stats_slab / ctl / stats as there (ctl nullable: separate finalize launch).
+ * pack / dec_pack / sched / stats_slab / ctl / stats as there (ctl nullable: stats_slab's spare words).
  * Bayesian kinds take the pack of ude_pack_weights_bayes.  y_hat equals ude_rk4_forward_dec's bit for
  * bit.  Replaces model(x, t, n_samples, training=False)'s odeint + Decoder (lib/utils.py:21). */
 int ude_rk4_forecast_dec(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,

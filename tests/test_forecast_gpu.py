@@ -139,6 +139,36 @@ def test_forecast_solve_bitwise_toy64(pkg):
     _assert_same(_both_solves(ode, z, t, step, lin))
 
 
+def test_forecast_dec_without_ctl_is_the_same_solve(pkg):
+    """ude_rk4_forecast_dec with ``ctl = NULL`` (the spare control word behind stats_slab, zeroed by the
+    call) against the plan's caller-zeroed ``ctl``: the same bits, the NULL call repeated on the same
+    buffers included, and the plan's words left zero."""
+    from ude_amd import fused
+    from ude_amd.forecast import _forecast_plan
+    from test_legacy_cabi import dirty_words
+    ode, z, t, step, lin, _ = _vae_inputs("e2e_vae_toy64")
+    plan = _forecast_plan(ode, z, t, step)
+    dev, sz = z.device, plan.sizes
+    pack = fused.packed_weights(plan, [p for l in ode.ude_linears() for p in (l.weight, l.bias)], dev)
+    dec_pack = torch.empty(sz.dec_pack_bytes // 4, dtype=torch.float32, device=dev)
+    plan.lib.pack_decoder(plan.desc, lin.weight.data_ptr(), lin.bias.data_ptr(), dec_pack.data_ptr(), fused._stream(dev))
+    ctl = fused._ctl(plan, dev)
+    res = []
+    stats_slab = torch.empty(sz.stats_slab_bytes // 8, dtype=torch.float64, device=dev)
+    dirty_words(stats_slab, sz.ctl_bytes)                          # the spare words start out non-zero
+    for c in (ctl.data_ptr(), None, None):
+        yhat = torch.empty((plan.n_times, z.shape[0], z.shape[1]), dtype=torch.float32, device=dev)
+        stats, sums, st = fused._stats_out(plan, dev)
+        plan.lib.forecast_dec(plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), z.data_ptr(),
+                              dec_pack.data_ptr(), yhat.data_ptr(), stats_slab.data_ptr(), c, st, fused._stream(dev))
+        res.append([yhat, *stats, sums])
+    torch.cuda.synchronize()
+    for other in res[1:]:
+        for a, b in zip(res[0], other):
+            assert torch.equal(a, b)
+    assert int(ctl.abs().max()) == 0
+
+
 def test_forecast_solve_bitwise_r10(pkg):
     g = load_golden("fafp_r10_weekly")
     mod = module_from_golden(pkg, g, "cuda")

@@ -17,7 +17,7 @@ import os
 import sys
 from collections import defaultdict
 
-KERNELS = {"bwd": "ude_bwd_kernel", "fwd": "ude_fwd_kernel", "finalize": "ude_grad_finalize_kernel"}
+KERNELS = {"bwd": "ude_bwd_kernel", "fwd": "ude_fwd_kernel", "tail": "ude_bwd_tail_kernel"}
 
 
 def per_kernel(d, counter):
