@@ -120,6 +120,27 @@ __device__ __forceinline__ int fc_count_below(const double* tile, int c, int G, 
   return lo;
 }
 
+// bitonic network along the rows (a power of two) of every column of tile [rows][G], ascending: rows / 2
+// compare-exchanges per column and stage over all threads.  Moves values only, so what it sorts keeps its bits.
+__device__ __forceinline__ void fc_bitonic_sort(double* tile, int rows, int rr, int c, int G, int RP) {
+  const int half = rows >> 1;
+  for (int k = 2; k <= rows; k <<= 1) {
+    for (int j = k >> 1; j > 0; j >>= 1) {
+      __syncthreads();
+      for (int p = rr; p < half; p += RP) {
+        const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
+        const double x = tile[i * G + c], y = tile[l * G + c];
+        const bool up = (i & k) == 0;
+        if ((x > y) == up) {
+          tile[i * G + c] = y;
+          tile[l * G + c] = x;
+        }
+      }
+    }
+  }
+  __syncthreads();
+}
+
 template <bool VERIFY>
 __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyArgs& v) {
   extern __shared__ __attribute__((aligned(16))) double fc_lds[];
@@ -161,23 +182,7 @@ __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyA
   }
 
   if (VERIFY || a.n_q > 0) {
-    // bitonic network along S: rows / 2 compare-exchanges per column and stage over all threads
-    const int half = rows >> 1;
-    for (int k = 2; k <= rows; k <<= 1) {
-      for (int j = k >> 1; j > 0; j >>= 1) {
-        __syncthreads();
-        for (int p = rr; p < half; p += RP) {
-          const int i = ((p & ~(j - 1)) << 1) | (p & (j - 1)), l = i | j;
-          const double x = tile[i * G + c], y = tile[l * G + c];
-          const bool up = (i & k) == 0;
-          if ((x > y) == up) {
-            tile[i * G + c] = y;
-            tile[l * G + c] = x;
-          }
-        }
-      }
-    }
-    __syncthreads();
+    fc_bitonic_sort(tile, rows, rr, c, G, RP);
     if (live) {
       for (int k = rr; k < a.n_q; k += RP)
         a.quant[(((size_t)k * a.B + b) * a.T + t) * a.R + r] = fc_quantile(tile, c, G, a.S, a.q[k]);

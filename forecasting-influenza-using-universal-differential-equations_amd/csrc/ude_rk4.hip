@@ -6,6 +6,7 @@
 #include "ude_entry.h"
 #include "ude_vec.h"      // model-independent vector kernels (compiled in both passes)
 #include "ude_forecast.h" // model-independent ensemble summary kernels (likewise)
+#include "ude_season.h"   // model-independent seasonal-target kernels (likewise)
 
 // This translation unit is host code only (no kernels are instantiated here).
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -326,6 +327,19 @@ int ude_forecast_verify(int32_t T, int32_t S, int32_t B, int32_t R, const float*
                         double* day, double* region, ude_stream_t stream) {
   return ude::forecast_verify(T, S, B, R, yhat, scale, y_true, q, n_q, alpha, n_alpha, n_pit, ws, mean, std, quant,
                               scores, day, region, (hipStream_t)stream);
+}
+
+int ude_forecast_season_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int32_t start,
+                                  int32_t every, int32_t run, int32_t window, int64_t* ws_bytes) {
+  return ude::forecast_season_workspace(T, S, B, R, n_q, start, every, run, window, ws_bytes);
+}
+
+int ude_forecast_season(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every, int32_t run,
+                        int32_t window, const float* yhat, const double* scale, const double* base,
+                        const float* y_true, const double* q, int32_t n_q, void* ws, double* stats, double* quant,
+                        double* peak_time, double* onset, double* overall, double* region, ude_stream_t stream) {
+  return ude::forecast_season(T, S, B, R, start, every, run, window, yhat, scale, base, y_true, q, n_q, ws, stats,
+                              quant, peak_time, onset, overall, region, (hipStream_t)stream);
 }
 
 #ifdef UDE_PROFILE

@@ -210,7 +210,8 @@ class VAE:
         self._pred_src = (y_pred, n_samples, B, None, None) if training else None
         return y_pred
 
-    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False):
+    def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False,
+                 season=None):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
@@ -230,7 +231,14 @@ class VAE:
         (ude_rk4_forecast_dyn; still no latent); a CPU model, a Bayesian RHS (evaluated at its mean
         weights), output times between grid points or an RHS without a kernel take them from the
         written latent instead (``ude_amd.forecast.latent_dynamics``), without touching
-        ``ode.params`` / ``ode.tracker``.  With ``dynamics=False`` nothing changes."""
+        ``ode.params`` / ``ode.tracker``.  With ``dynamics=False`` nothing changes.
+
+        ``season`` -- an ``ude_amd.forecast.Season`` -- also fills ``Forecast.season``
+        (``ude_amd.forecast.SeasonTargets``): over the output times it considers, the ensemble's
+        distribution of each trajectory's peak value, peak time, total and (with a baseline) onset, and
+        with targets their scores against the observed season, from the same prediction on every route
+        (ude_forecast_season on the device: the prediction is still not copied to the host).  With
+        ``season=None`` nothing changes."""
         B = x.shape[0]
         dev_is_hip = torch.device(self.device).type == "cuda"
         lin = decoder_head.decoder_linear(self.dec)
@@ -266,6 +274,9 @@ class VAE:
                                                quantiles=quantiles, verify=verify)
             if dynamics:
                 fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
+            if season is not None:
+                fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,
+                                                         quantiles=quantiles)
             return fc
         y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
         if not self.uncertainty:
@@ -276,6 +287,9 @@ class VAE:
         if dynamics:
             dyn = ude_forecast.latent_dynamics(self.ode, self.latent)
             fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
+        if season is not None:
+            fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,
+                                                     quantiles=quantiles)
         return fc
 
     def _fused_head(self, y_pred, y_true, losses):

@@ -160,6 +160,8 @@ _CABI: Dict[str, tuple] = {
     "ude_forecast_summary": _sig("forecast_summary", (4, _i32), (4, _vp), _i32, (6, _vp)),
     "ude_forecast_verify_workspace": _sig(None, (7, _i32), _pi64),
     "ude_forecast_verify": _sig("forecast_verify", (4, _i32), (4, _vp), _i32, _vp, (2, _i32), (8, _vp)),
+    "ude_forecast_season_workspace": _sig(None, (9, _i32), _pi64),
+    "ude_forecast_season": _sig("forecast_season", (8, _i32), (5, _vp), _i32, (8, _vp)),
     "ude_build_info": _sig(None),
 }
 EXPORTED_SYMBOLS = tuple(_CABI)
@@ -254,6 +256,9 @@ class NativeLib:
 
     def forecast_verify_workspace(self, T, S, B, R, n_q, n_alpha, n_pit) -> int:
         return self._workspace("ude_forecast_verify_workspace", T, S, B, R, n_q, n_alpha, n_pit)
+
+    def forecast_season_workspace(self, T, S, B, R, n_q, start, every, run, window) -> int:
+        return self._workspace("ude_forecast_season_workspace", T, S, B, R, n_q, start, every, run, window)
 
     def lincomb(self, n, base, ks: Sequence[int], coef, out, stream) -> None:
         arr = (ctypes.c_void_p * len(ks))(*ks)

@@ -24,6 +24,11 @@ gamma the rate net gives at that state, R_eff = beta S / gamma, and the augmenta
 ``(C, T, N, R)`` array that ``dynamics_summary`` turns into a ``Dynamics`` by one ``ensemble_summary``
 call.  ``latent_dynamics`` forms the same channels from a written latent (CPU, Bayesian RHS, output
 times between grid points).
+
+``ensemble_season`` reduces the same ``y_hat`` along its trajectories instead of per day
+(ude_forecast_season): per sample the peak over the considered output times, when it falls, the total
+and the onset against a baseline -- the FluSight seasonal targets -- as a ``SeasonTargets`` of their
+distributions over the ensemble, scored against the observed season when targets are given.
 """
 from __future__ import annotations
 
@@ -61,6 +66,112 @@ class Verify:
             raise ValueError("Verify: every alpha must lie in (0, 1)")
         if int(self.pit_bins) != self.pit_bins or not 1 <= self.pit_bins <= MAX_PIT_BINS:
             raise ValueError(f"Verify: pit_bins {self.pit_bins} (1 to {MAX_PIT_BINS})")
+
+
+@dataclass(frozen=True)
+class Season:
+    """What ``season=`` considers.  The output indices ``t_m = start + m * every``, ``m = 0 .. M-1`` with
+    ``M = ceil((T - start) / every)`` (weekly points of a daily grid: ``start=6, every=7``); ``baseline``:
+    None (no onset), a number or one per region, in scaled units; the onset is the first ``m`` that starts
+    ``run`` consecutive considered values at or above the baseline; ``window``: the half-width, in
+    considered times, of the bins the peak-time and onset log scores count as a hit."""
+    baseline: Optional[object] = None
+    start: int = 0
+    every: int = 1
+    run: int = 3
+    window: int = 1
+
+    def __post_init__(self):
+        for name, low in (("start", 0), ("every", 1), ("run", 1), ("window", 0)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or int(v) < low or int(v) > 2 ** 31 - 1:
+                raise ValueError(f"Season: {name} {v!r} (an integer >= {low})")
+            object.__setattr__(self, name, int(v))
+        if self.baseline is not None:
+            base = np.asarray(self.baseline.values if hasattr(self.baseline, "values") else self.baseline,
+                              dtype=np.float64)
+            if base.ndim > 1 or base.size < 1 or not np.isfinite(base).all():
+                raise ValueError("Season: baseline is a finite number or one per region")
+            object.__setattr__(self, "baseline", float(base) if base.ndim == 0 else tuple(base.tolist()))
+
+    def times(self, T: int) -> int:
+        """M, the number of considered output indices of a T-point forecast."""
+        if not self.start < T:
+            raise ValueError(f"Season: start {self.start} is not below the {T} output times")
+        return -((self.start - T) // self.every)
+
+    def baseline_vector(self, R: int, device) -> Optional[torch.Tensor]:
+        if self.baseline is None:
+            return None
+        base = torch.as_tensor(self.baseline, dtype=torch.float64, device=device).reshape(-1)
+        if base.numel() == 1:
+            base = base.expand(R)
+        if base.numel() != R:
+            raise ValueError(f"Season: baseline has {base.numel()} entries for {R} regions")
+        return base.contiguous()
+
+
+SEASON_SCORES = ("peak_time_skill", "onset_skill", "peak_value_skill", "peak_crps", "total_crps")
+
+
+@dataclass
+class SeasonTargets:
+    """The seasonal targets of an ensemble forecast (fp64 tensors on the forecast's device), over the M
+    considered output indices of a ``Season``.  Per (window, region) group over the S trajectories:
+    ``peak_mean`` / ``peak_std`` (B, R) and ``peak_quantiles`` (Q, B, R) or None of each trajectory's
+    highest considered value; ``total_*``: the same of each trajectory's sum; ``peak_time`` (B, M, R): the
+    fraction of trajectories whose peak falls on index m (the first, where several tie); ``onset``
+    (B, M + 1, R) or None without a baseline: the fraction whose onset is m, bin M being "no onset within
+    the horizon".
+
+    With targets, against the observed season (the same rules on ``y_true``): ``peak_time_skill`` /
+    ``onset_skill`` = exp(mean log mass the histogram gives to the bins within ``window`` of the observed
+    one; "none" only matches "none"), ``peak_value_skill`` = exp(mean log empirical mass of the multibin
+    window around the observed peak), an empty window or zero mass counting as MASS_FLOOR; ``peak_crps``
+    / ``total_crps``.  Each is the mean over the B * R groups (0-dim); ``*_r`` (R,) per region over the B
+    windows."""
+    peak_mean: torch.Tensor
+    peak_std: torch.Tensor
+    total_mean: torch.Tensor
+    total_std: torch.Tensor
+    peak_time: torch.Tensor
+    peak_quantiles: Optional[torch.Tensor] = None
+    total_quantiles: Optional[torch.Tensor] = None
+    onset: Optional[torch.Tensor] = None
+    peak_time_skill: Optional[torch.Tensor] = None
+    onset_skill: Optional[torch.Tensor] = None
+    peak_value_skill: Optional[torch.Tensor] = None
+    peak_crps: Optional[torch.Tensor] = None
+    total_crps: Optional[torch.Tensor] = None
+    peak_time_skill_r: Optional[torch.Tensor] = None
+    onset_skill_r: Optional[torch.Tensor] = None
+    peak_value_skill_r: Optional[torch.Tensor] = None
+    peak_crps_r: Optional[torch.Tensor] = None
+    total_crps_r: Optional[torch.Tensor] = None
+
+    def _tensors(self):
+        return [(f.name, getattr(self, f.name)) for f in fields(self) if getattr(self, f.name) is not None]
+
+    def _map(self, fn) -> "SeasonTargets":
+        return SeasonTargets(**{n: fn(v) for n, v in self._tensors()})
+
+    def cpu(self) -> "SeasonTargets":
+        """One stacked device-to-host copy."""
+        parts = self._tensors()
+        if not parts[0][1].is_cuda:
+            return self
+        flat = torch.cat([v.reshape(-1) for _, v in parts]).cpu()
+        out, o = {}, 0
+        for n, v in parts:
+            out[n] = flat[o:o + v.numel()].view(v.shape)
+            o += v.numel()
+        return SeasonTargets(**out)
+
+    def numpy(self):
+        """dict of numpy arrays (absent fields None)."""
+        host = self.cpu()
+        return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
+                for f in fields(host)}
 
 
 DYN_STATE = ("s", "i", "r")
@@ -133,7 +244,8 @@ class Forecast:
     ``coverage_r`` (K, T, R).
 
     ``dynamics``: the ``Dynamics`` of the same ensemble when it was asked for
-    (``VAE.forecast(dynamics=True)``), else None."""
+    (``VAE.forecast(dynamics=True)``), else None.  ``season``: its ``SeasonTargets``
+    (``VAE.forecast(season=Season(...))``), else None."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
@@ -153,35 +265,37 @@ class Forecast:
     ens_skill_r: Optional[torch.Tensor] = None
     coverage_r: Optional[torch.Tensor] = None
     dynamics: Optional[Dynamics] = None
+    season: Optional[SeasonTargets] = None
 
     def _map(self, fn):
         return Forecast(**{f.name: (None if getattr(self, f.name) is None
-                                    else getattr(self, f.name)._map(fn) if f.name == "dynamics"
+                                    else getattr(self, f.name)._map(fn) if f.name in ("dynamics", "season")
                                     else fn(getattr(self, f.name)))
                            for f in fields(self)})
 
     def cpu(self) -> "Forecast":
-        """One stacked device-to-host copy of every field (the dynamics' tensors included)."""
-        names = [f.name for f in fields(self) if f.name != "dynamics" and getattr(self, f.name) is not None]
+        """One stacked device-to-host copy of every field (the dynamics' and the season's tensors included)."""
+        names = [f.name for f in fields(self)
+                 if f.name not in ("dynamics", "season") and getattr(self, f.name) is not None]
         parts = [getattr(self, n) for n in names]
         if not parts[0].is_cuda:
             return self
-        dyn = [] if self.dynamics is None else self.dynamics._tensors()
-        flat = torch.cat([p.reshape(-1) for p in parts + [v for _, v in dyn]]).cpu()
+        nested = {n: getattr(self, n)._tensors() for n in ("dynamics", "season") if getattr(self, n) is not None}
+        flat = torch.cat([p.reshape(-1) for p in parts + [v for ts in nested.values() for _, v in ts]]).cpu()
         out, o = {}, 0
         for n, p in zip(names, parts):
             out[n] = flat[o:o + p.numel()].view(p.shape)
             o += p.numel()
-        if self.dynamics is not None:
+        for name, ts in nested.items():
             host = {}
-            for n, v in dyn:
+            for n, v in ts:
                 host[n] = flat[o:o + v.numel()].view(v.shape)
                 o += v.numel()
-            out["dynamics"] = Dynamics(self.dynamics.names, **host)
+            out[name] = Dynamics(self.dynamics.names, **host) if name == "dynamics" else SeasonTargets(**host)
         return Forecast(**out)
 
     def numpy(self):
-        """dict of numpy arrays (absent fields None; ``dynamics``: ``Dynamics.numpy()``'s dict)."""
+        """dict of numpy arrays (absent fields None; ``dynamics`` / ``season``: their ``numpy()`` dicts)."""
         host = self.cpu()
         return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
                 for f in fields(host)}
@@ -360,6 +474,145 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
         out.nll_r, out.skill_r, out.mae_r = region[0], region[1].exp(), region[2]
         out.crps_r, out.wis_r, out.ens_skill_r = region[3], region[4], region[5].exp()
         out.coverage_r = region[6:]
+    return out
+
+
+def _season_walk(v: torch.Tensor, base: Optional[torch.Tensor], run: int):
+    """``(peak, when, total, onset or None)`` over dim 0 of ``v`` (M, ..., R) (scaled fp64): the largest
+    value, the first index that attains it, the sum with m ascending, and with ``base`` (R,) the first m
+    that starts ``run`` consecutive values at or above it, M where there is none."""
+    M = v.shape[0]
+    idx = torch.arange(M, device=v.device).view(M, *([1] * (v.dim() - 1)))
+    peak = v.amax(0)
+    when = torch.where(v == peak, idx, M).amin(0)
+    total = v[0].clone()
+    for m in range(1, M):
+        total = total + v[m]
+    if base is None:
+        return peak, when, total, None
+    onset = torch.full_like(when, M)
+    if run <= M:
+        above = torch.cat([torch.zeros_like(v[:1], dtype=torch.int64), (v >= base).to(torch.int64).cumsum(0)])
+        hit = (above[run:] - above[:M - run + 1]) == run                                  # (M - run + 1, ...)
+        onset = torch.where(hit, idx[:M - run + 1], M).amin(0)
+    return peak, when, total, onset
+
+
+def _sorted_crps(xs: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
+    """ude_forecast_verify's CRPS of the samples ``xs`` (S, ...), sorted along dim 0, against ``y``."""
+    S = xs.shape[0]
+    rank = (torch.arange(S, dtype=torch.float64, device=xs.device) * 2 - (S - 1)).view(S, *([1] * (xs.dim() - 1)))
+    return (xs - y).abs().sum(0) / S - (rank * xs).sum(0) / (S * S)
+
+
+def _floored_log(count: torch.Tensor, S: int) -> torch.Tensor:
+    return torch.where(count == 0, torch.full(count.shape, MASS_FLOOR, dtype=torch.float64, device=count.device),
+                       count.to(torch.float64) / S).log()
+
+
+def _season_torch(yhat, S, B, season: Season, M, y_true, scale, base, q) -> SeasonTargets:
+    T, N, R = yhat.shape
+    v = yhat.detach()[season.start::season.every].to(torch.float64).reshape(M, S, B, R)
+    if scale is not None:
+        v = v * scale
+    peak, when, total, onset = _season_walk(v, base, season.run)                          # (S, B, R)
+    stat = lambda x: (x.mean(0), ((x - x.mean(0)) ** 2).mean(0).sqrt())
+    hist = lambda i, n: torch.nn.functional.one_hot(i, n).sum(0)                           # (B, R, n) counts
+    n_when = hist(when, M)
+    out = SeasonTargets(*stat(peak), *stat(total), (n_when.to(torch.float64) / S).permute(0, 2, 1).contiguous())
+    ps, ts = peak.sort(dim=0).values, total.sort(dim=0).values
+    if q is not None and q.numel() > 0:
+        out.peak_quantiles = _lerp_quantile(ps.unsqueeze(0), q)[:, 0].contiguous()
+        out.total_quantiles = _lerp_quantile(ts.unsqueeze(0), q)[:, 0].contiguous()
+    n_onset = None
+    if onset is not None:
+        n_onset = hist(onset, M + 1)
+        out.onset = (n_onset.to(torch.float64) / S).permute(0, 2, 1).contiguous()
+    if y_true is None:
+        return out
+    y = y_true.detach().to(torch.float64).permute(1, 0, 2)[season.start::season.every]      # (M, B, R)
+    if scale is not None:
+        y = y * scale
+    y_peak, y_when, y_total, y_onset = _season_walk(y, base, season.run)                   # (B, R)
+    bins = torch.arange(M + 1, device=v.device)
+    near = lambda o: ((bins - o.unsqueeze(-1)).abs() <= season.window) & (bins < M)       # (B, R, M + 1)
+    logs = [_floored_log((n_when * near(y_when)[..., :M]).sum(-1), S)]
+    if onset is not None:
+        mask = torch.where((y_onset == M).unsqueeze(-1), bins == M, near(y_onset))
+        logs.append(_floored_log((n_onset * mask).sum(-1), S))
+    else:
+        logs.append(None)
+    cb = (y_peak * 10.0).floor() / 10.0
+    logs.append(_floored_log(((peak >= cb - 0.5) & (peak < cb + 0.6)).sum(0), S))
+    terms = logs + [_sorted_crps(ps, y_peak), _sorted_crps(ts, y_total)]
+    for name, term in zip(SEASON_SCORES, terms):
+        if term is None:
+            continue
+        skill = name.endswith("_skill")
+        setattr(out, name, term.mean().exp() if skill else term.mean())
+        setattr(out, name + "_r", term.mean(0).exp() if skill else term.mean(0))
+    return out
+
+
+def ensemble_season(values: torch.Tensor, n_samples: int, batch: int, season: Season,
+                    y_true: Optional[torch.Tensor] = None, scale=None,
+                    quantiles: Optional[Sequence[float]] = None) -> SeasonTargets:
+    """The seasonal targets of ``values`` (T, S*B, R) fp32 (sample n = s*B + b: ``y_hat`` as the solve
+    emits it, or one dynamics channel ``dyn[c]``) over the output indices ``season`` considers: see
+    ``SeasonTargets``.  ``scale`` / ``y_true`` (B, T, R) / ``quantiles`` as ``ensemble_summary`` takes them;
+    ``season.baseline`` is in scaled units.  A HIP tensor runs ude_forecast_season (one read of the
+    considered values, n_samples <= 1024); a CPU tensor (or no library) the same definitions in torch
+    fp64."""
+    if not isinstance(season, Season):
+        raise TypeError("ensemble_season: season is a Season")
+    if values.dim() != 3 or values.shape[1] != n_samples * batch:
+        raise ValueError(f"ensemble_season: values {tuple(values.shape)} are not (T, {n_samples}*{batch}, R)")
+    T, N, R = (int(v) for v in values.shape)
+    S, B = int(n_samples), int(batch)
+    if y_true is not None and tuple(y_true.shape) != (B, T, R):
+        raise ValueError(f"ensemble_season: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
+    M = season.times(T)
+    dev = values.device
+    sc = _scale_vector(scale, R, dev)
+    base = season.baseline_vector(R, dev)
+    q = None
+    if quantiles is not None and len(quantiles) > 0:
+        q = torch.as_tensor(np.asarray(quantiles, dtype=np.float64), device=dev)
+        if bool(((q < 0) | (q > 1)).any()):
+            raise ValueError("ensemble_season: quantile levels must lie in [0, 1]")
+    if S > MAX_QUANTILE_SAMPLES and values.is_cuda:
+        raise ValueError(f"ensemble_season: n_samples <= {MAX_QUANTILE_SAMPLES} on the device")
+    lib = _library() if values.is_cuda else None
+    if lib is None:
+        return _season_torch(values, S, B, season, M, y_true, sc, base, q)
+    n_q = 0 if q is None else int(q.numel())
+    yh = values.detach().to(torch.float32).contiguous()
+    yt = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
+    opts = (season.start, season.every, season.run, season.window)
+    with torch.cuda.device(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        stats = torch.empty((4, B, R), **f64)
+        quant = torch.empty((2, n_q, B, R), **f64) if n_q else None
+        peak_time = torch.empty((B, M, R), **f64)
+        onset = torch.empty((B, M + 1, R), **f64) if base is not None else None
+        overall = torch.empty(len(SEASON_SCORES), **f64) if yt is not None else None
+        region = torch.empty((len(SEASON_SCORES), R), **f64) if yt is not None else None
+        ws = torch.empty(lib.forecast_season_workspace(T, S, B, R, n_q, *opts) // 8, **f64) if yt is not None else None
+        p = _fused._ptr
+        with _fused._timed("forecast_season"):
+            lib.forecast_season(T, S, B, R, *opts, yh.data_ptr(), p(sc), p(base), p(yt), p(q), n_q, p(ws),
+                                stats.data_ptr(), p(quant), peak_time.data_ptr(), p(onset), p(overall), p(region),
+                                _fused._stream(dev))
+    out = SeasonTargets(stats[0], stats[1], stats[2], stats[3], peak_time, onset=onset)
+    if quant is not None:
+        out.peak_quantiles, out.total_quantiles = quant[0], quant[1]
+    if yt is not None:
+        for k, name in enumerate(SEASON_SCORES):
+            if name == "onset_skill" and base is None:
+                continue
+            skill = name.endswith("_skill")
+            setattr(out, name, overall[k].exp() if skill else overall[k])
+            setattr(out, name + "_r", region[k].exp() if skill else region[k])
     return out
 
 

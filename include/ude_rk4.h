@@ -425,6 +425,41 @@ int ude_forecast_verify(int32_t T, int32_t S, int32_t B, int32_t R, const float*
                         int32_t n_pit, void* ws, double* mean, double* std, double* quant, double* scores,
                         double* day, double* region, ude_stream_t stream);
 
+/* ude_forecast_season: the seasonal targets of y_hat (T, S*B, R) (sample n = s*B + b; no model) -- what
+ * depends on how a trajectory's output times hang together.  The considered output indices are t_m = start +
+ * m * every, m = 0 .. M-1, M = ceil((T - start) / every) (weekly points of a daily grid: start 6, every 7);
+ * the others are never read.  For a group (b, r) and sample s, fp64 after the fp32 load:
+ *   v[m]   = (double)y_hat[t_m, s*B+b, r] * scale[r]
+ *   peak_s = max_m v[m],   when_s = the smallest m that attains it (numpy.argmax),
+ *   total_s = sum_m v[m] (m ascending),
+ *   onset_s = the smallest m <= M - run with v[m+k] >= base[r] for all k < run, else M ("no onset within the
+ *             horizon"; equality counts as at or above; base (R,) in scaled units, nullable: no onset)
+ * Per group over the S samples (S <= 1024; NaN inputs undefined):
+ *   stats (4, B, R)        mean and population std (ddof 0, two passes) of peak_s, then of total_s
+ *   quant (2, n_q, B, R)   numpy.quantile ('linear') at q[k] of peak_s, then of total_s
+ *   peak_time (B, M, R)    #{when_s = m} / S
+ *   onset (B, M + 1, R)    #{onset_s = m} / S (only with base; bin M is "none")
+ * Counts are integers, divided once.  With targets, y[m] = (double)y_true[b, t_m, r] * scale[r] gives the
+ * observed y* = max, m* = its first index, o* and sum y by the same rules (-1 targets are not masked), and per
+ * group, with an exactly zero P or an empty window replaced by 4.5399929762484854e-05,
+ *   0  log P, P = sum over |m - m*| <= window, 0 <= m <= M-1, of peak_time[m]
+ *   1  log P, P = onset[M] if o* = M, else the sum over |m - o*| <= window, m < M, of onset[m] (0 without base)
+ *   2  log(#{c - 0.5 <= peak_s < c + 0.6} / S), c = floor(10 y*) / 10 (ude_forecast_verify's mass, on the peaks)
+ *   3  crps of peak_s against y*,   4  crps of total_s against sum y   (ude_forecast_verify's sorted-sample
+ *      formula: sum_i |x_i - y| / S - sum_i (2 i - S + 1) x_(i) / S^2)
+ * overall (5,): the mean over the B*R groups; region (5, R): the mean over the B windows (skills are exp of
+ * terms 0 - 2).  Fixed-order sums, no atomics: the same bits run to run.  start in [0, T), every >= 1,
+ * run >= 1 (run > M is legal: no sample has an onset), window >= 0; UDE_E_INVALID otherwise.  quant nullable
+ * with n_q = 0; onset only read with base; ws (ude_forecast_season_workspace() bytes), overall and region only
+ * with y_true.  Every considered element of y_hat is read exactly once.  The reference has no counterpart:
+ * it replaces a host copy of the whole (B, S, T, R) prediction and NumPy over its trajectories. */
+int ude_forecast_season_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int32_t start,
+                                  int32_t every, int32_t run, int32_t window, int64_t* ws_bytes);
+int ude_forecast_season(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every, int32_t run,
+                        int32_t window, const float* yhat, const double* scale, const double* base,
+                        const float* y_true, const double* q, int32_t n_q, void* ws, double* stats, double* quant,
+                        double* peak_time, double* onset, double* overall, double* region, ude_stream_t stream);
+
 /* Library build tag (for logs / tests). */
 const char* ude_build_info(void);
 

@@ -22,11 +22,20 @@ paths taking turns:
   (b) fused: model.forecast(x, t, 128, y_true, scaler, dynamics=True).cpu();
   (c) the forecast without dynamics, (b) of the default mode, for the solve kernel's time without DYN.
 
+``--season`` times the seasonal targets (weekly points of the daily grid: start 6, every 7, a baseline per
+region, targets given) of one y_hat (57, 8192, 49) resident on the device, two routes taking turns:
+
+  (a) host: a device-to-host copy of y_hat, then NumPy forming the same quantities over the trajectories
+      (peak, peak week, total, onset per sample; mean / std / histograms per group; the log scores and the
+      sorted-sample CRPS against the observed season);
+  (b) device: ude_amd.forecast.ensemble_season(...).cpu() -- ude_forecast_season and one stacked copy of
+      its results.
+
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
 (ude_amd.fused.EVENTS).  Prints one JSON line.
 
-    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128] [--dynamics]
+    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128] [--dynamics | --season]
 """
 import argparse
 import importlib
@@ -92,6 +101,7 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--dynamics", action="store_true", help="time the dynamics paths instead (see the docstring)")
+    ap.add_argument("--season", action="store_true", help="time the seasonal targets instead (see the docstring)")
     a = ap.parse_args()
     R, B, S, window = 49, a.batch, a.samples, 8
     torch.manual_seed(0)
@@ -132,6 +142,71 @@ def main():
                                   text=True).stdout.strip() or None
         except OSError:
             return None
+
+    if a.season:
+        from ude_amd import forecast as fcast
+        T = len(t)
+        base = np.median(y_test.cpu().numpy().astype(np.float64) * scaler, axis=(0, 1))
+        season = fcast.Season(baseline=base, start=6, every=7)
+        with torch.no_grad():
+            yhat = model(x, t, n_samples=S, training=False).permute(2, 1, 0, 3).reshape(T, S * B, R).contiguous()
+        floor = fcast.MASS_FLOOR
+
+        def host_route(e1=None):
+            v = yhat.cpu().numpy()                                              # the copy the device route saves
+            if e1 is not None:
+                e1.record()
+            y = y_test.cpu().numpy().astype(np.float64).transpose(1, 0, 2)[6::7] * scaler      # (M, B, R)
+            v = v.astype(np.float64).reshape(T, S, B, R)[6::7] * scaler                        # (M, S, B, R)
+            M = v.shape[0]
+
+            def walk(u):
+                above = np.concatenate([np.zeros_like(u[:1], dtype=np.int64), (u >= base).cumsum(0)])
+                hit = (above[season.run:] - above[:M - season.run + 1]) == season.run
+                onset = np.where(hit.any(0), hit.argmax(0), M)
+                return u.max(0), u.argmax(0), u.sum(0), onset
+
+            peak, when, total, onset = walk(v)
+            y_peak, y_when, y_total, y_onset = walk(y)
+            n_when = np.stack([(when == m).sum(0) for m in range(M)])                          # (M, B, R)
+            n_onset = np.stack([(onset == m).sum(0) for m in range(M + 1)])
+            bins = np.arange(M + 1).reshape(-1, 1, 1)
+            near = lambda o: (np.abs(bins - o) <= season.window) & (bins < M)
+            flog = lambda n: np.log(np.where(n == 0, floor, n / S))
+            cb = np.floor(10 * y_peak) / 10
+            rank = (2 * np.arange(S) - S + 1).reshape(-1, 1, 1)
+            crps = lambda u, z: np.abs(u - z).sum(0) / S - (rank * np.sort(u, axis=0)).sum(0) / (S * S)
+            terms = [flog((n_when * near(y_when)[:M]).sum(0)),
+                     flog((n_onset * np.where(y_onset == M, bins == M, near(y_onset))).sum(0)),
+                     flog(((peak >= cb - 0.5) & (peak < cb + 0.6)).sum(0)), crps(peak, y_peak), crps(total, y_total)]
+            return {"peak_mean": peak.mean(0), "peak_std": peak.std(0), "total_mean": total.mean(0),
+                    "total_std": total.std(0), "peak_time": n_when / S, "onset": n_onset / S,
+                    "scores": [float(u.mean()) for u in terms], "scores_r": [u.mean(0) for u in terms]}
+
+        def device_route(e1=None):
+            st = fcast.ensemble_season(yhat, S, B, season, y_true=y_test, scale=scaler).cpu()
+            if e1 is not None:
+                e1.record()
+            return st
+
+        ha, st = host_route(), device_route()
+        got = [float(st.peak_time_skill.log()), float(st.onset_skill.log()), float(st.peak_value_skill.log()),
+               float(st.peak_crps), float(st.total_crps)]
+        agree = max(abs(p - q) / max(abs(q), 1e-30) for p, q in zip(got, ha["scores"]))
+        same_hist = bool(np.array_equal(st.peak_time.numpy().transpose(1, 0, 2), ha["peak_time"]) and
+                         np.array_equal(st.onset.numpy().transpose(1, 0, 2), ha["onset"]))
+        res_a, res_b = timed_alternating([host_route, device_route], a.runs, a.warmup)
+        from ude_amd import _native
+        print(json.dumps({"tool": "forecast_timing --season", "commit": commit_of(),
+                          "device": torch.cuda.get_device_name(0),
+                          "shape": {"R": R, "S": S, "B": B, "N": S * B, "T": T, "M": season.times(T)},
+                          "yhat_bytes": T * S * B * R * 4, "considered_bytes": season.times(T) * S * B * R * 4,
+                          "result_bytes": sum(int(v.numel()) * 8 for _, v in st._tensors()),
+                          "workspace_bytes": _native.prebuilt().forecast_season_workspace(T, S, B, R, 0, 6, 7, 3, 1),
+                          "scores_rel_diff_device_vs_host": agree, "histograms_equal": same_hist,
+                          "host_route": res_a, "device_route": res_b,
+                          "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}))
+        return
 
     if a.dynamics:
         from ude_amd import eval_rhs
