@@ -35,6 +35,7 @@ constexpr int FC_MAX_PIT = 64;           // PIT histogram bins
 constexpr int FC_TERMS = 7;              // per-group terms: nll, log mass, |y - mean|, crps, wis, log
                                          // empirical mass, coverage bits (bit k: interval k holds y)
 constexpr int FC_DEAD_BIN = 255;         // PIT bin of a column past B R
+constexpr double FC_MASS_FLOOR = 4.5399929762484854e-05;   // lib/Metrics.py mb_log: an exactly zero mass -> e^-10
 
 struct FcGeom {
   int rows;      // tile rows: S, or its power-of-two padding when sorting; 0 = no tile (S too large)
@@ -141,6 +142,71 @@ __device__ __forceinline__ void fc_bitonic_sort(double* tile, int rows, int rr, 
   __syncthreads();
 }
 
+// The ensemble statistics of one column, stated once for the summary / verify kernel and the season
+// kernel (ude_season.h).  All threads of the workgroup call them (they go through fc_col_sum); thread
+// row rr takes the samples rr, rr + RP, ..
+
+struct FcMoments { double mean, sd; };
+
+// mean and population std (two passes) of val(0) .. val(S - 1)
+template <class Val>
+__device__ __forceinline__ FcMoments fc_col_moments(double* red, Val val, int S, int rr, int c, int G, int RP) {
+  FcMoments m;
+  double acc = 0.0;
+  for (int s = rr; s < S; s += RP) acc += val(s);
+  m.mean = fc_col_sum(red, acc, rr, c, G, RP) / (double)S;
+  acc = 0.0;
+  for (int s = rr; s < S; s += RP) {
+    const double d = val(s) - m.mean;
+    acc += d * d;
+  }
+  m.sd = sqrt(fc_col_sum(red, acc, rr, c, G, RP) / (double)S);
+  return m;
+}
+
+// CRPS of the S sorted rows x_0 <= .. of column c against y: mean |x_i - y| - sum (2 i - S + 1) x_i / S^2
+__device__ __forceinline__ double fc_col_crps(double* red, const double* tile, double y, int S, int rr, int c, int G,
+                                              int RP) {
+  double w = 0.0, ad = 0.0;
+  for (int i = rr; i < S; i += RP) {
+    const double x = tile[i * G + c];
+    w += (double)(2 * i - S + 1) * x;
+    ad += fabs(x - y);
+  }
+  const double wsum = fc_col_sum(red, w, rr, c, G, RP);
+  const double asum = fc_col_sum(red, ad, rr, c, G, RP);
+  const double dS = (double)S;
+  return asum / dS - wsum / (dS * dS);
+}
+
+// log of the mass the S sorted rows of column c give the multibin window [cb - 0.5, cb + 0.6),
+// cb = floor(10 y) / 10 (lib/Metrics.py mb_log(bins=True)); an empty window counts as FC_MASS_FLOOR.
+// One thread's work: no fc_col_sum.
+__device__ __forceinline__ double fc_window_log_mass(const double* tile, int c, int G, int S, double y) {
+  const double cb = floor(y * 10.0) / 10.0;
+  const int n = fc_count_below<false>(tile, c, G, S, cb + 0.6) - fc_count_below<false>(tile, c, G, S, cb - 0.5);
+  return log(n == 0 ? FC_MASS_FLOOR : (double)n / (double)S);
+}
+
+// The two fixed-order sums of the reduce kernels (no atomics: the same bits run to run).
+// One wave: entry k of the partials first .. first + n - 1 of part [..][width], lane-strided then a fixed
+// butterfly; every lane has the sum
+__device__ __forceinline__ double fc_wave_sum(const double* part, size_t first, int n, int width, int k, int ln) {
+  double s = 0.0;
+  for (int i = ln; i < n; i += 64) s += part[(first + i) * width + k];
+#pragma unroll
+  for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+  return s;
+}
+
+// One thread: (p[0] + p[R] + .. + p[(B - 1) R], in that order) / B
+__device__ __forceinline__ double fc_group_mean(const double* p, int B, int R) {
+  double acc = 0.0;
+#pragma unroll 8
+  for (int b = 0; b < B; ++b) acc += p[(size_t)b * R];
+  return acc / (double)B;
+}
+
 template <bool VERIFY>
 __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyArgs& v) {
   extern __shared__ __attribute__((aligned(16))) double fc_lds[];
@@ -166,15 +232,8 @@ __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyA
     return live ? (double)src[(size_t)s * BR] * sc : 0.0;
   };
   if (tiled) __syncthreads();
-  double acc = 0.0;
-  for (int s = rr; s < a.S; s += RP) acc += val(s);
-  const double mean = fc_col_sum(red, acc, rr, c, G, RP) / (double)a.S;
-  acc = 0.0;
-  for (int s = rr; s < a.S; s += RP) {
-    const double d = val(s) - mean;
-    acc += d * d;
-  }
-  const double sd = sqrt(fc_col_sum(red, acc, rr, c, G, RP) / (double)a.S);
+  const FcMoments mo = fc_col_moments(red, val, a.S, rr, c, G, RP);
+  const double mean = mo.mean, sd = mo.sd;
   const size_t o = ((size_t)b * a.T + t) * a.R + r;
   if (live && rr == 0) {
     a.mean[o] = mean;
@@ -195,7 +254,7 @@ __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyA
       const double y = (double)a.y_true[o] * sc, z = (y - mean) / sd;
       t0 = 0.5 * z * z + log(sd) + 0.91893853320467274178;
       double mass = fc_ndtr((y + 0.6 - mean) / sd) - fc_ndtr((y - 0.5 - mean) / sd);
-      if (mass == 0.0) mass = 4.5399929762484854e-05;
+      if (mass == 0.0) mass = FC_MASS_FLOOR;
       t1 = log(mass);
       t2 = fabs(y - mean);
     }
@@ -223,15 +282,8 @@ __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyA
 
   if constexpr (VERIFY) {
     // the ensemble's own scores from the sorted tile (targets are given: checked by the host)
-    const double y = live ? (double)a.y_true[o] * sc : 0.0, dS = (double)a.S;
-    double w = 0.0, ad = 0.0;
-    for (int i = rr; i < a.S; i += RP) {
-      const double x = tile[i * G + c];
-      w += (double)(2 * i - a.S + 1) * x;
-      ad += fabs(x - y);
-    }
-    const double wsum = fc_col_sum(red, w, rr, c, G, RP);
-    const double asum = fc_col_sum(red, ad, rr, c, G, RP);
+    const double y = live ? (double)a.y_true[o] * sc : 0.0;
+    const double crps = fc_col_crps(red, tile, y, a.S, rr, c, G, RP);
     double iv = 0.0, bits = 0.0;                   // interval k of thread row k mod RP
     for (int k = rr; k < v.K; k += RP) {
       const double al = v.alpha[k];
@@ -243,15 +295,12 @@ __device__ __forceinline__ void fc_summary_body(const FcArgs& a, const FcVerifyA
     const double cover = fc_col_sum(red, bits, rr, c, G, RP);   // distinct bits: the sum is their union
     double t3 = 0.0, t4 = 0.0, t5 = 0.0, packed = (double)(FC_DEAD_BIN << 16);
     if (live && rr == 0) {
-      t3 = asum / dS - wsum / (dS * dS);
+      t3 = crps;
       t4 = (0.5 * fabs(y - fc_quantile(tile, c, G, a.S, 0.5)) + ivsum) / ((double)v.K + 0.5);
       const int n_lt = fc_count_below<false>(tile, c, G, a.S, y), n_le = fc_count_below<true>(tile, c, G, a.S, y);
       int bin = (v.J * (n_lt + n_le)) / (2 * a.S);
       if (bin > v.J - 1) bin = v.J - 1;
-      const double cb = floor(y * 10.0) / 10.0;
-      const int n_win = fc_count_below<false>(tile, c, G, a.S, cb + 0.6) -
-                        fc_count_below<false>(tile, c, G, a.S, cb - 0.5);
-      t5 = log(n_win == 0 ? 4.5399929762484854e-05 : (double)n_win / dS);
+      t5 = fc_window_log_mass(tile, c, G, a.S, y);
       packed = cover + (double)(bin << 16);
       double* tg = v.terms + ((size_t)t * FC_TERMS + 3) * BR + g;
       tg[0] = t3;
@@ -293,24 +342,20 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_verify_kernel(FcArgs 
   fc_summary_body<true>(a, v);
 }
 
-// scores[k][t] = (sum over the workgroups of t, lane-strided then a fixed butterfly) / (B R)
+// scores[k][t] = (fc_wave_sum over the workgroups of t) / (B R)
 __global__ __launch_bounds__(64) void ude_forecast_scores_kernel(const double* __restrict__ part, int nbx, int T,
                                                                  double inv_n, double* __restrict__ scores) {
   const int t = blockIdx.x, ln = threadIdx.x;
   for (int k = 0; k < 3; ++k) {
-    double s = 0.0;
-    for (int i = ln; i < nbx; i += 64) s += part[((size_t)t * nbx + i) * 3 + k];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    const double s = fc_wave_sum(part, (size_t)t * nbx, nbx, 3, k, ln);
     if (ln == 0) scores[(size_t)k * T + t] = s * inv_n;
   }
 }
 
 // The VERIFY outputs, one workgroup of FC_TERMS waves per (64 regions, t); wave f takes term f.
-// vreg[f][t][r] = the sum over b = 0 .. B-1, in that order, of the group terms / B: f < 6 the six scores,
-// 6 + k the coverage of interval k (an integer count, divided once).  The first workgroup of each t also
-// forms vday[k][t] = (sum over the workgroup partials of t, as ude_forecast_scores_kernel sums them) /
-// (B R), k < 3 + K + J, wave f those with k = f mod FC_TERMS.
+// vreg[f][t][r] = fc_group_mean of the group terms over b: f < 6 the six scores, 6 + k the coverage of
+// interval k (an integer count, divided once).  The first workgroup of each t also forms vday[k][t] =
+// (fc_wave_sum over the workgroup partials of t) / (B R), k < 3 + K + J, wave f those with k = f mod FC_TERMS.
 __global__ __launch_bounds__(64 * FC_TERMS) void ude_forecast_verify_reduce_kernel(
     const double* __restrict__ vpart, const double* __restrict__ terms, int nbx, int T, int B, int R, int K, int J,
     double* __restrict__ vday, double* __restrict__ vreg) {
@@ -319,10 +364,7 @@ __global__ __launch_bounds__(64 * FC_TERMS) void ude_forecast_verify_reduce_kern
   if (blockIdx.x == 0) {
     const int NP = 3 + K + J;
     for (int k = f; k < NP; k += FC_TERMS) {
-      double s = 0.0;
-      for (int i = ln; i < nbx; i += 64) s += vpart[((size_t)t * nbx + i) * NP + k];
-#pragma unroll
-      for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+      const double s = fc_wave_sum(vpart, (size_t)t * nbx, nbx, NP, k, ln);
       if (ln == 0) vday[(size_t)k * T + t] = s / (double)BR;
     }
   }
@@ -330,10 +372,7 @@ __global__ __launch_bounds__(64 * FC_TERMS) void ude_forecast_verify_reduce_kern
   if (r >= R) return;
   const double* p = terms + ((size_t)t * FC_TERMS + f) * BR + r;
   if (f < 6) {
-    double acc = 0.0;
-#pragma unroll 8
-    for (int b = 0; b < B; ++b) acc += p[(size_t)b * R];
-    vreg[((size_t)f * T + t) * R + r] = acc / (double)B;
+    vreg[((size_t)f * T + t) * R + r] = fc_group_mean(p, B, R);
   } else {
     int cnt[FC_MAX_ALPHA] = {};
 #pragma unroll 8
@@ -360,18 +399,27 @@ inline int forecast_summary_workspace(int T, int S, int B, int R, int n_q, int64
   return 0;
 }
 
+// What forecast_summary and forecast_verify (sorted: it always sorts its tile) share: the checks of the
+// shape and of the pointers both take, the kernel's arguments, its geometry and its dynamic LDS bytes.
+inline bool fc_launch_args(int T, int S, int B, int R, const float* yhat, const double* scale, const float* y_true,
+                           const double* q, int n_q, void* ws, double* mean, double* std, double* quant, bool sorted,
+                           FcArgs* a, FcGeom* ge, size_t* lds) {
+  if (!fc_shape_ok(T, S, B, R, n_q) || !yhat || !mean || !std) return false;
+  if (n_q > 0 && (!q || !quant)) return false;
+  *a = FcArgs{yhat, scale, y_true, q, mean, std, quant, (double*)ws, T, S, B, R, n_q};
+  *ge = fc_geom(S, B * R, sorted ? 1 : n_q);
+  *lds = ((size_t)FC_THREADS + (size_t)ge->rows * ge->G) * 8;
+  return true;
+}
+
 inline int forecast_summary(int T, int S, int B, int R, const float* yhat, const double* scale, const float* y_true,
                             const double* q, int n_q, void* ws, double* mean, double* std, double* quant,
                             double* scores, hipStream_t s) {
-  if (!fc_shape_ok(T, S, B, R, n_q) || !yhat || !mean || !std) return -2;
-  if (n_q > 0 && (!q || !quant)) return -2;
-  if (y_true && (!ws || !scores)) return -2;
-  const FcGeom ge = fc_geom(S, B * R, n_q);
   FcArgs a;
-  a.yhat = yhat; a.scale = scale; a.y_true = y_true; a.q = q;
-  a.mean = mean; a.std = std; a.quant = quant; a.part = (double*)ws;
-  a.T = T; a.S = S; a.B = B; a.R = R; a.n_q = n_q;
-  const size_t lds = ((size_t)FC_THREADS + (size_t)ge.rows * ge.G) * 8;
+  FcGeom ge;
+  size_t lds;
+  if (!fc_launch_args(T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, false, &a, &ge, &lds)) return -2;
+  if (y_true && (!ws || !scores)) return -2;
   hipLaunchKernelGGL(ude_forecast_summary_kernel, dim3(ge.nbx, T), dim3(FC_THREADS), lds, s, a);
   if (hipGetLastError() != hipSuccess) return -3;
   if (y_true) {
@@ -397,19 +445,16 @@ inline int forecast_verify_workspace(int T, int S, int B, int R, int n_q, int K,
 inline int forecast_verify(int T, int S, int B, int R, const float* yhat, const double* scale, const float* y_true,
                            const double* q, int n_q, const double* alpha, int K, int J, void* ws, double* mean,
                            double* std, double* quant, double* scores, double* vday, double* vreg, hipStream_t s) {
-  if (!fc_verify_ok(T, S, B, R, n_q, K, J) || !yhat || !mean || !std) return -2;
-  if (n_q > 0 && (!q || !quant)) return -2;
-  if (!y_true || !alpha || !ws || !scores || !vday || !vreg) return -2;
-  const FcGeom ge = fc_geom(S, B * R, 1);
   FcArgs a;
-  a.yhat = yhat; a.scale = scale; a.y_true = y_true; a.q = q;
-  a.mean = mean; a.std = std; a.quant = quant; a.part = (double*)ws;
-  a.T = T; a.S = S; a.B = B; a.R = R; a.n_q = n_q;
+  FcGeom ge;
+  size_t lds;
+  if (!fc_verify_ok(T, S, B, R, n_q, K, J)) return -2;
+  if (!fc_launch_args(T, S, B, R, yhat, scale, y_true, q, n_q, ws, mean, std, quant, true, &a, &ge, &lds)) return -2;
+  if (!y_true || !alpha || !ws || !scores || !vday || !vreg) return -2;
   FcVerifyArgs v;
   v.alpha = alpha; v.K = K; v.J = J;
   v.vpart = a.part + (size_t)T * ge.nbx * 3;
   v.terms = v.vpart + (size_t)T * ge.nbx * (3 + K + J);
-  const size_t lds = ((size_t)FC_THREADS + (size_t)ge.rows * ge.G) * 8;
   hipLaunchKernelGGL(ude_forecast_verify_kernel, dim3(ge.nbx, T), dim3(FC_THREADS), lds, s, a, v);
   if (hipGetLastError() != hipSuccess) return -3;
   hipLaunchKernelGGL(ude_forecast_scores_kernel, dim3(T), dim3(64), 0, s, (const double*)ws, ge.nbx, T,

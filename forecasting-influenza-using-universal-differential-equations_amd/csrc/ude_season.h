@@ -33,9 +33,7 @@ namespace ude {
 constexpr int FS_BATCH = 8;              // loads of one sample in flight
 constexpr int FS_TERMS = 5;              // log P(peak time), log P(onset), log P(peak value), crps peak, crps total
 
-#ifndef UDE_FS_CELLS
-#define UDE_FS_CELLS (FC_TILE_ELEMS / 4) // rows G of a workgroup (an A/B build may override it; see above)
-#endif
+constexpr int UDE_FS_CELLS = FC_TILE_ELEMS / 4;   // rows G of a workgroup (the measurement above)
 
 __host__ __device__ inline FcGeom fs_geom(int S, int BR) {
   FcGeom g = fc_geom(S, BR, 1);
@@ -147,18 +145,10 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_season_kernel(FsArgs 
   const int b = live ? g / a.R : 0, r = live ? g - b * a.R : 0;
   const double dS = (double)a.S;
 
-  double acc = 0.0;
-  for (int s = rr; s < a.S; s += RP) acc += V[s * G2 + c2];
-  const double mean = fc_col_sum(red, acc, rr, c2, G2, RP) / dS;
-  acc = 0.0;
-  for (int s = rr; s < a.S; s += RP) {
-    const double d = V[s * G2 + c2] - mean;
-    acc += d * d;
-  }
-  const double sd = sqrt(fc_col_sum(red, acc, rr, c2, G2, RP) / dS);
+  const FcMoments mo = fc_col_moments(red, [&](int s) { return V[s * G2 + c2]; }, a.S, rr, c2, G2, RP);
   if (live && rr == 0) {
-    a.stats[(size_t)(2 * which) * BR + g] = mean;
-    a.stats[(size_t)(2 * which + 1) * BR + g] = sd;
+    a.stats[(size_t)(2 * which) * BR + g] = mo.mean;
+    a.stats[(size_t)(2 * which + 1) * BR + g] = mo.sd;
   }
 
   fc_bitonic_sort(V, rows, rr, c2, G2, RP);
@@ -186,7 +176,7 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_season_kernel(FsArgs 
   // the window counts of the two time scores and the sorted-sample CRPS sums of the two value columns
   const int ostar = which ? obs_onset[c] : obs_when[c];
   const double y = which ? obs_total[c] : obs_peak[c];
-  double cnt = 0.0, w = 0.0, ad = 0.0;
+  double cnt = 0.0;
   {
     const int* idx = which ? on : wh;
     const bool none = which && ostar == M;        // observed: no onset within the horizon
@@ -195,27 +185,15 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_season_kernel(FsArgs 
       const int d = i > ostar ? i - ostar : ostar - i;
       cnt += none ? (double)(i == M) : (double)(i < M && d <= a.window);
     }
-    for (int i = rr; i < a.S; i += RP) {
-      const double x = V[i * G2 + c2];
-      w += (double)(2 * i - a.S + 1) * x;
-      ad += fabs(x - y);
-    }
   }
   const double nwin = fc_col_sum(red, cnt, rr, c2, G2, RP);
-  const double wsum = fc_col_sum(red, w, rr, c2, G2, RP);
-  const double asum = fc_col_sum(red, ad, rr, c2, G2, RP);
+  const double col_crps = fc_col_crps(red, V, y, a.S, rr, c2, G2, RP);
   if (rr == 0) {
     double lt = 0.0, lv = 0.0, crps = 0.0;        // dead columns add zero to the partials
     if (live) {
-      const double floor_mass = 4.5399929762484854e-05;
-      lt = (which && !has_base) ? 0.0 : log(nwin == 0.0 ? floor_mass : nwin / dS);
-      crps = asum / dS - wsum / (dS * dS);
-      if (!which) {
-        const double cb = floor(y * 10.0) / 10.0;
-        const int n_val = fc_count_below<false>(V, c2, G2, a.S, cb + 0.6) -
-                          fc_count_below<false>(V, c2, G2, a.S, cb - 0.5);
-        lv = log(n_val == 0 ? floor_mass : (double)n_val / dS);
-      }
+      lt = (which && !has_base) ? 0.0 : log(nwin == 0.0 ? FC_MASS_FLOOR : nwin / dS);
+      crps = col_crps;
+      if (!which) lv = fc_window_log_mass(V, c2, G2, a.S, y);
       a.terms[(size_t)which * BR + g] = lt;                       // 0: peak time, 1: onset
       a.terms[(size_t)(3 + which) * BR + g] = crps;               // 3: peak, 4: total
       if (!which) a.terms[(size_t)2 * BR + g] = lv;
@@ -232,28 +210,21 @@ __global__ __launch_bounds__(FC_THREADS) void ude_forecast_season_kernel(FsArgs 
   }
 }
 
-// One workgroup of FS_TERMS waves per 64 regions; wave f takes term f.  region[f][r] = the sum over
-// b = 0 .. B-1, in that order, of the group terms / B.  The first workgroup also forms overall[f] = (sum
-// over the workgroup partials, lane-strided then a fixed butterfly) / (B R).
+// One workgroup of FS_TERMS waves per 64 regions; wave f takes term f.  region[f][r] = fc_group_mean of
+// the group terms over b.  The first workgroup also forms overall[f] = (fc_wave_sum over the workgroup
+// partials) / (B R).
 __global__ __launch_bounds__(64 * FS_TERMS) void ude_forecast_season_reduce_kernel(
     const double* __restrict__ part, const double* __restrict__ terms, int nbx, int B, int R,
     double* __restrict__ overall, double* __restrict__ region) {
   const int ln = threadIdx.x, f = threadIdx.y;
   const size_t BR = (size_t)B * R;
   if (blockIdx.x == 0) {
-    double s = 0.0;
-    for (int i = ln; i < nbx; i += 64) s += part[(size_t)i * FS_TERMS + f];
-#pragma unroll
-    for (int m = 32; m >= 1; m >>= 1) s += __shfl_xor(s, m, 64);
+    const double s = fc_wave_sum(part, 0, nbx, FS_TERMS, f, ln);
     if (ln == 0) overall[f] = s / (double)BR;
   }
   const int r = blockIdx.x * 64 + ln;
   if (r >= R) return;
-  const double* p = terms + (size_t)f * BR + r;
-  double acc = 0.0;
-#pragma unroll 8
-  for (int b = 0; b < B; ++b) acc += p[(size_t)b * R];
-  region[(size_t)f * R + r] = acc / (double)B;
+  region[(size_t)f * R + r] = fc_group_mean(terms + (size_t)f * BR + r, B, R);
 }
 
 // M, the number of considered times, or 0 when the arguments are out of range

@@ -270,22 +270,15 @@ class VAE:
                     yhat = self.dec(self.latent[..., :3]).reshape(len(t), n_samples * B, self.n_regions)
                     if dynamics:
                         dyn = ude_forecast.latent_dynamics(self.ode, self.latent)
-            fc = ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler,
-                                               quantiles=quantiles, verify=verify)
-            if dynamics:
-                fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
-            if season is not None:
-                fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,
-                                                         quantiles=quantiles)
-            return fc
-        y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
-        if not self.uncertainty:
-            n_samples = 1
-        yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
+        else:
+            y_pred = self(x, t, n_samples=n_samples, training=False)             # (B, S, T, R)
+            if not self.uncertainty:
+                n_samples = 1
+            yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
+            dyn = ude_forecast.latent_dynamics(self.ode, self.latent) if dynamics else None
         fc = ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles,
                                            verify=verify)
         if dynamics:
-            dyn = ude_forecast.latent_dynamics(self.ode, self.latent)
             fc.dynamics = ude_forecast.dynamics_summary(dyn[0], dyn[1], n_samples, B, quantiles=quantiles)
         if season is not None:
             fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,

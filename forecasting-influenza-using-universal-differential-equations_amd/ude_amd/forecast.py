@@ -114,8 +114,49 @@ class Season:
 SEASON_SCORES = ("peak_time_skill", "onset_skill", "peak_value_skill", "peak_crps", "total_crps")
 
 
+class _Result:
+    """What the result containers (dataclasses) share.  A field holds a tensor, None, another container
+    (``Forecast.dynamics`` / ``.season``: handled by recursion) or something else that is carried through
+    (``Dynamics.names``)."""
+
+    def _tensors(self):
+        """``[(field name, tensor)]`` in field order, a nested container's in its place."""
+        out = []
+        for f in fields(self):
+            v = getattr(self, f.name)
+            if isinstance(v, _Result):
+                out += v._tensors()
+            elif isinstance(v, torch.Tensor):
+                out.append((f.name, v))
+        return out
+
+    def _map(self, fn):
+        """The same container with ``fn`` applied to every tensor, in the order of ``_tensors``."""
+        def go(v):
+            return v._map(fn) if isinstance(v, _Result) else fn(v) if isinstance(v, torch.Tensor) else v
+        return type(self)(**{f.name: go(getattr(self, f.name)) for f in fields(self)})
+
+    def cpu(self):
+        """One stacked device-to-host copy of every tensor (nested containers' included); ``self`` when
+        already on the host."""
+        parts = [v for _, v in self._tensors()]
+        if not parts[0].is_cuda:
+            return self
+        chunks = iter(torch.cat([v.reshape(-1) for v in parts]).cpu().split([v.numel() for v in parts]))
+        return self._map(lambda v: next(chunks).view(v.shape))
+
+    def numpy(self):
+        """dict of numpy arrays by field name (absent fields None; a nested container: its ``numpy()`` dict;
+        ``Dynamics.names`` as it is)."""
+        host, out = self.cpu(), {}
+        for f in fields(host):
+            v = getattr(host, f.name)
+            out[f.name] = v.numpy() if isinstance(v, (_Result, torch.Tensor)) else v
+        return out
+
+
 @dataclass
-class SeasonTargets:
+class SeasonTargets(_Result):
     """The seasonal targets of an ensemble forecast (fp64 tensors on the forecast's device), over the M
     considered output indices of a ``Season``.  Per (window, region) group over the S trajectories:
     ``peak_mean`` / ``peak_std`` (B, R) and ``peak_quantiles`` (Q, B, R) or None of each trajectory's
@@ -149,30 +190,6 @@ class SeasonTargets:
     peak_crps_r: Optional[torch.Tensor] = None
     total_crps_r: Optional[torch.Tensor] = None
 
-    def _tensors(self):
-        return [(f.name, getattr(self, f.name)) for f in fields(self) if getattr(self, f.name) is not None]
-
-    def _map(self, fn) -> "SeasonTargets":
-        return SeasonTargets(**{n: fn(v) for n, v in self._tensors()})
-
-    def cpu(self) -> "SeasonTargets":
-        """One stacked device-to-host copy."""
-        parts = self._tensors()
-        if not parts[0][1].is_cuda:
-            return self
-        flat = torch.cat([v.reshape(-1) for _, v in parts]).cpu()
-        out, o = {}, 0
-        for n, v in parts:
-            out[n] = flat[o:o + v.numel()].view(v.shape)
-            o += v.numel()
-        return SeasonTargets(**out)
-
-    def numpy(self):
-        """dict of numpy arrays (absent fields None)."""
-        host = self.cpu()
-        return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
-                for f in fields(host)}
-
 
 DYN_STATE = ("s", "i", "r")
 DYN_RATES = ("beta", "gamma", "r_eff")
@@ -187,7 +204,7 @@ def dynamics_names(ode) -> Tuple[str, ...]:
 
 
 @dataclass
-class Dynamics:
+class Dynamics(_Result):
     """Per-(channel, window, day, region) summary of the learned dynamics over the ensemble (fp64):
     ``names`` (C channel names, ``dynamics_names``), ``mean`` / ``std`` (C, B, T, R) (population std)
     and ``quantiles`` (Q, C, B, T, R) or None.  ``dyn["r_eff"]`` is that channel's
@@ -203,33 +220,9 @@ class Dynamics:
         c = self.names.index(name)
         return self.mean[c], self.std[c], (None if self.quantiles is None else self.quantiles[:, c])
 
-    def _tensors(self):
-        return [(n, getattr(self, n)) for n in ("mean", "std", "quantiles") if getattr(self, n) is not None]
-
-    def _map(self, fn) -> "Dynamics":
-        return Dynamics(self.names, **{n: fn(v) for n, v in self._tensors()})
-
-    def cpu(self) -> "Dynamics":
-        """One stacked device-to-host copy."""
-        parts = self._tensors()
-        if not parts[0][1].is_cuda:
-            return self
-        flat = torch.cat([v.reshape(-1) for _, v in parts]).cpu()
-        out, o = {}, 0
-        for n, v in parts:
-            out[n] = flat[o:o + v.numel()].view(v.shape)
-            o += v.numel()
-        return Dynamics(self.names, **out)
-
-    def numpy(self):
-        """dict: ``names`` and the numpy arrays (``quantiles`` None when absent)."""
-        host = self.cpu()
-        return {"names": host.names, "mean": host.mean.numpy(), "std": host.std.numpy(),
-                "quantiles": None if host.quantiles is None else host.quantiles.numpy()}
-
 
 @dataclass
-class Forecast:
+class Forecast(_Result):
     """Per-(window, day, region) summary of an ensemble forecast (fp64 tensors on the forecast's
     device): ``mean`` / ``std`` (B, T, R) (population std, as numpy.std), ``quantiles`` (Q, B, T, R)
     or None, and -- when targets were given -- ``nll`` / ``skill`` / ``mae`` (T,): lib/Metrics.py's
@@ -266,39 +259,6 @@ class Forecast:
     coverage_r: Optional[torch.Tensor] = None
     dynamics: Optional[Dynamics] = None
     season: Optional[SeasonTargets] = None
-
-    def _map(self, fn):
-        return Forecast(**{f.name: (None if getattr(self, f.name) is None
-                                    else getattr(self, f.name)._map(fn) if f.name in ("dynamics", "season")
-                                    else fn(getattr(self, f.name)))
-                           for f in fields(self)})
-
-    def cpu(self) -> "Forecast":
-        """One stacked device-to-host copy of every field (the dynamics' and the season's tensors included)."""
-        names = [f.name for f in fields(self)
-                 if f.name not in ("dynamics", "season") and getattr(self, f.name) is not None]
-        parts = [getattr(self, n) for n in names]
-        if not parts[0].is_cuda:
-            return self
-        nested = {n: getattr(self, n)._tensors() for n in ("dynamics", "season") if getattr(self, n) is not None}
-        flat = torch.cat([p.reshape(-1) for p in parts + [v for ts in nested.values() for _, v in ts]]).cpu()
-        out, o = {}, 0
-        for n, p in zip(names, parts):
-            out[n] = flat[o:o + p.numel()].view(p.shape)
-            o += p.numel()
-        for name, ts in nested.items():
-            host = {}
-            for n, v in ts:
-                host[n] = flat[o:o + v.numel()].view(v.shape)
-                o += v.numel()
-            out[name] = Dynamics(self.dynamics.names, **host) if name == "dynamics" else SeasonTargets(**host)
-        return Forecast(**out)
-
-    def numpy(self):
-        """dict of numpy arrays (absent fields None; ``dynamics`` / ``season``: their ``numpy()`` dicts)."""
-        host = self.cpu()
-        return {f.name: (None if getattr(host, f.name) is None else getattr(host, f.name).numpy())
-                for f in fields(host)}
 
 
 def _scale_vector(scale, R: int, device) -> Optional[torch.Tensor]:
@@ -339,13 +299,36 @@ def _lerp_quantile(vs: torch.Tensor, q: torch.Tensor) -> torch.Tensor:
     return torch.where(gm >= 0.5, y - d * (1.0 - gm), x + d * gm)
 
 
+def _sorted_crps(xs: torch.Tensor, y: torch.Tensor, dim: int = 0, v: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The kernels' CRPS (fc_col_crps) of the samples ``xs``, sorted along ``dim``, against ``y`` (xs's
+    shape without ``dim``).  ``v``: the tensor whose ``|v - y|`` are summed when it is not ``xs``
+    (``_verify_torch`` sums the unsorted samples: another order, other bits)."""
+    S = xs.shape[dim]
+    rank = (torch.arange(S, dtype=torch.float64, device=xs.device) * 2 - (S - 1)).view(
+        [S if d == dim else 1 for d in range(xs.dim())])
+    return ((xs if v is None else v) - y.unsqueeze(dim)).abs().sum(dim) / S - (rank * xs).sum(dim) / (S * S)
+
+
+def _floored_log(count: torch.Tensor, S: int) -> torch.Tensor:
+    """log(count / S), an exactly zero count as MASS_FLOOR."""
+    return torch.where(count == 0, torch.full(count.shape, MASS_FLOOR, dtype=torch.float64, device=count.device),
+                       count.to(torch.float64) / S).log()
+
+
+def _window_log_mass(v: torch.Tensor, y: torch.Tensor, dim: int) -> torch.Tensor:
+    """The kernels' fc_window_log_mass: the floored log of the fraction of the samples ``v`` (along ``dim``)
+    in the multibin window ``[cb - 0.5, cb + 0.6)``, ``cb = floor(10 y) / 10``, of ``y`` (v's shape without
+    ``dim``)."""
+    cb = (y * 10.0).floor() / 10.0
+    return _floored_log(((v >= (cb - 0.5).unsqueeze(dim)) & (v < (cb + 0.6).unsqueeze(dim))).sum(dim), v.shape[dim])
+
+
 def _verify_torch(out: Forecast, v, y, mean, nll, mass, verify: Verify) -> None:
     """The ``verify`` fields from v (T, S, B, R) and y / mean / nll / mass (T, B, R), all scaled fp64."""
     T, S, B, R = v.shape
     n = float(B * R)
     vs = v.sort(dim=1).values
-    rank = torch.arange(S, dtype=torch.float64, device=v.device) * 2 - (S - 1)
-    crps = (v - y.unsqueeze(1)).abs().sum(1) / S - (rank.view(1, S, 1, 1) * vs).sum(1) / (S * S)
+    crps = _sorted_crps(vs, y, 1, v)
     al = torch.tensor(verify.alphas, dtype=torch.float64, device=v.device)
     K, J = al.numel(), int(verify.pit_bins)
     lo, up = _lerp_quantile(vs, 0.5 * al), _lerp_quantile(vs, 1.0 - 0.5 * al)          # (K, T, B, R)
@@ -356,15 +339,13 @@ def _verify_torch(out: Forecast, v, y, mean, nll, mass, verify: Verify) -> None:
     cover = ((lo <= y) & (y <= up)).to(torch.float64)
     mid = (v < y.unsqueeze(1)).sum(1) + (v <= y.unsqueeze(1)).sum(1)                   # n_lt + n_le
     pit_bin = torch.div(J * mid, 2 * S, rounding_mode="floor").clamp(max=J - 1)
-    cb = (y * 10.0).floor() / 10.0
-    n_win = ((v >= (cb - 0.5).unsqueeze(1)) & (v < (cb + 0.6).unsqueeze(1))).sum(1)
-    emp = torch.where(n_win == 0, torch.full_like(y, MASS_FLOOR), n_win.to(torch.float64) / S)
+    log_emp = _window_log_mass(v, y, 1)
     out.crps, out.wis = crps.mean((1, 2)), wis.mean((1, 2))
-    out.ens_skill = emp.log().mean((1, 2)).exp()
+    out.ens_skill = log_emp.mean((1, 2)).exp()
     out.coverage = cover.sum((2, 3)) / n
     out.pit = torch.nn.functional.one_hot(pit_bin, J).to(torch.float64).sum((1, 2)) / n
     out.nll_r, out.skill_r, out.mae_r = nll.mean(1), mass.log().mean(1).exp(), (y - mean).abs().mean(1)
-    out.crps_r, out.wis_r, out.ens_skill_r = crps.mean(1), wis.mean(1), emp.log().mean(1).exp()
+    out.crps_r, out.wis_r, out.ens_skill_r = crps.mean(1), wis.mean(1), log_emp.mean(1).exp()
     out.coverage_r = cover.sum(2) / float(B)
 
 
@@ -404,6 +385,34 @@ def _library() -> Optional["_native.NativeLib"]:
     return None
 
 
+def _prepare(who: str, values, n_samples, batch, y_true, scale, quantiles, sorts: bool):
+    """The arguments ``ensemble_summary`` and ``ensemble_season`` (``who``, for the messages) share, checked:
+    ``(T, S, B, R, device, scale (R,) fp64 or None, levels fp64 or None, their number, lib, values, y_true)``.
+    ``sorts``: the kernel sorts its tile whatever the levels, so the device's sample cap holds without them.
+    ``lib`` is None where the torch definitions run (a CPU tensor, no library); otherwise ``values`` and
+    ``y_true`` come back as the kernels read them, fp32 and contiguous on the device."""
+    if values.dim() != 3 or values.shape[1] != n_samples * batch:
+        raise ValueError(f"{who}: values {tuple(values.shape)} are not (T, {n_samples}*{batch}, R)")
+    T, N, R = (int(v) for v in values.shape)
+    S, B = int(n_samples), int(batch)
+    if y_true is not None and tuple(y_true.shape) != (B, T, R):
+        raise ValueError(f"{who}: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
+    dev = values.device
+    sc = _scale_vector(scale, R, dev)
+    q = None
+    if quantiles is not None and len(quantiles) > 0:
+        q = torch.as_tensor(np.asarray(quantiles, dtype=np.float64), device=dev)
+        if bool(((q < 0) | (q > 1)).any()):
+            raise ValueError(f"{who}: quantile levels must lie in [0, 1]")
+    if (sorts or q is not None) and S > MAX_QUANTILE_SAMPLES and values.is_cuda:
+        raise ValueError(f"{who}: n_samples <= {MAX_QUANTILE_SAMPLES} on the device (the kernel sorts its tile)")
+    lib = _library() if values.is_cuda else None
+    if lib is not None:
+        values = values.detach().to(torch.float32).contiguous()
+        y_true = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return T, S, B, R, dev, sc, q, (0 if q is None else int(q.numel())), lib, values, y_true
+
+
 def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Optional[torch.Tensor] = None,
                      scale=None, quantiles: Optional[Sequence[float]] = None, verify=None) -> Forecast:
     """Summary of ``yhat`` (T, S*B, R) (sample n = s*B + b, as the solve emits it) over its S
@@ -413,12 +422,6 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
     ensemble itself (``Forecast``); the other fields keep their bits.  A HIP tensor runs
     ude_forecast_summary (ude_forecast_verify with ``verify``, n_samples <= 1024); a CPU tensor (or no
     library) the same definitions in torch fp64."""
-    if yhat.dim() != 3 or yhat.shape[1] != n_samples * batch:
-        raise ValueError(f"ensemble_summary: y_hat {tuple(yhat.shape)} is not (T, {n_samples}*{batch}, R)")
-    T, N, R = (int(v) for v in yhat.shape)
-    S, B = int(n_samples), int(batch)
-    if y_true is not None and tuple(y_true.shape) != (B, T, R):
-        raise ValueError(f"ensemble_summary: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
     if verify is True:
         verify = Verify()
     if verify is not None:
@@ -426,23 +429,10 @@ def ensemble_summary(yhat: torch.Tensor, n_samples: int, batch: int, y_true: Opt
             raise TypeError("ensemble_summary: verify is None, True or a Verify")
         if y_true is None:
             raise ValueError("ensemble_summary: verify needs the targets y_true")
-        if S > MAX_QUANTILE_SAMPLES and yhat.is_cuda:
-            raise ValueError(f"ensemble_summary: verify needs n_samples <= {MAX_QUANTILE_SAMPLES}")
-    dev = yhat.device
-    sc = _scale_vector(scale, R, dev)
-    q = None
-    if quantiles is not None and len(quantiles) > 0:
-        q = torch.as_tensor(np.asarray(quantiles, dtype=np.float64), device=dev)
-        if bool(((q < 0) | (q > 1)).any()):
-            raise ValueError("ensemble_summary: quantile levels must lie in [0, 1]")
-        if S > MAX_QUANTILE_SAMPLES and yhat.is_cuda:
-            raise ValueError(f"ensemble_summary: quantiles need n_samples <= {MAX_QUANTILE_SAMPLES}")
-    lib = _library() if yhat.is_cuda else None
+    T, S, B, R, dev, sc, q, n_q, lib, yh, yt = _prepare("ensemble_summary", yhat, n_samples, batch, y_true, scale,
+                                                        quantiles, sorts=verify is not None)
     if lib is None:
         return _summary_torch(yhat, S, B, y_true, sc, q, verify)
-    n_q = 0 if q is None else int(q.numel())
-    yh = yhat.detach().to(torch.float32).contiguous()
-    yt = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
     with torch.cuda.device(dev):
         f64 = dict(dtype=torch.float64, device=dev)
         mean = torch.empty((B, T, R), **f64)
@@ -498,16 +488,15 @@ def _season_walk(v: torch.Tensor, base: Optional[torch.Tensor], run: int):
     return peak, when, total, onset
 
 
-def _sorted_crps(xs: torch.Tensor, y: torch.Tensor) -> torch.Tensor:
-    """ude_forecast_verify's CRPS of the samples ``xs`` (S, ...), sorted along dim 0, against ``y``."""
-    S = xs.shape[0]
-    rank = (torch.arange(S, dtype=torch.float64, device=xs.device) * 2 - (S - 1)).view(S, *([1] * (xs.dim() - 1)))
-    return (xs - y).abs().sum(0) / S - (rank * xs).sum(0) / (S * S)
-
-
-def _floored_log(count: torch.Tensor, S: int) -> torch.Tensor:
-    return torch.where(count == 0, torch.full(count.shape, MASS_FLOOR, dtype=torch.float64, device=count.device),
-                       count.to(torch.float64) / S).log()
+def _set_season_scores(out: SeasonTargets, overall, region, has_onset: bool) -> None:
+    """``overall[k]`` / ``region[k]`` of ``SEASON_SCORES[k]`` into ``out`` and its ``*_r`` fields.  Both
+    routes hold a skill as its mean log: ``exp`` on the way out.  Without a baseline there is no onset score."""
+    for k, name in enumerate(SEASON_SCORES):
+        if name == "onset_skill" and not has_onset:
+            continue
+        skill = name.endswith("_skill")
+        setattr(out, name, overall[k].exp() if skill else overall[k])
+        setattr(out, name + "_r", region[k].exp() if skill else region[k])
 
 
 def _season_torch(yhat, S, B, season: Season, M, y_true, scale, base, q) -> SeasonTargets:
@@ -542,15 +531,10 @@ def _season_torch(yhat, S, B, season: Season, M, y_true, scale, base, q) -> Seas
         logs.append(_floored_log((n_onset * mask).sum(-1), S))
     else:
         logs.append(None)
-    cb = (y_peak * 10.0).floor() / 10.0
-    logs.append(_floored_log(((peak >= cb - 0.5) & (peak < cb + 0.6)).sum(0), S))
+    logs.append(_window_log_mass(peak, y_peak, 0))
     terms = logs + [_sorted_crps(ps, y_peak), _sorted_crps(ts, y_total)]
-    for name, term in zip(SEASON_SCORES, terms):
-        if term is None:
-            continue
-        skill = name.endswith("_skill")
-        setattr(out, name, term.mean().exp() if skill else term.mean())
-        setattr(out, name + "_r", term.mean(0).exp() if skill else term.mean(0))
+    _set_season_scores(out, [t if t is None else t.mean() for t in terms],
+                       [t if t is None else t.mean(0) for t in terms], onset is not None)
     return out
 
 
@@ -565,29 +549,12 @@ def ensemble_season(values: torch.Tensor, n_samples: int, batch: int, season: Se
     fp64."""
     if not isinstance(season, Season):
         raise TypeError("ensemble_season: season is a Season")
-    if values.dim() != 3 or values.shape[1] != n_samples * batch:
-        raise ValueError(f"ensemble_season: values {tuple(values.shape)} are not (T, {n_samples}*{batch}, R)")
-    T, N, R = (int(v) for v in values.shape)
-    S, B = int(n_samples), int(batch)
-    if y_true is not None and tuple(y_true.shape) != (B, T, R):
-        raise ValueError(f"ensemble_season: targets {tuple(y_true.shape)} are not ({B}, {T}, {R})")
+    T, S, B, R, dev, sc, q, n_q, lib, yh, yt = _prepare("ensemble_season", values, n_samples, batch, y_true, scale,
+                                                        quantiles, sorts=True)
     M = season.times(T)
-    dev = values.device
-    sc = _scale_vector(scale, R, dev)
     base = season.baseline_vector(R, dev)
-    q = None
-    if quantiles is not None and len(quantiles) > 0:
-        q = torch.as_tensor(np.asarray(quantiles, dtype=np.float64), device=dev)
-        if bool(((q < 0) | (q > 1)).any()):
-            raise ValueError("ensemble_season: quantile levels must lie in [0, 1]")
-    if S > MAX_QUANTILE_SAMPLES and values.is_cuda:
-        raise ValueError(f"ensemble_season: n_samples <= {MAX_QUANTILE_SAMPLES} on the device")
-    lib = _library() if values.is_cuda else None
     if lib is None:
         return _season_torch(values, S, B, season, M, y_true, sc, base, q)
-    n_q = 0 if q is None else int(q.numel())
-    yh = values.detach().to(torch.float32).contiguous()
-    yt = None if y_true is None else y_true.detach().to(device=dev, dtype=torch.float32).contiguous()
     opts = (season.start, season.every, season.run, season.window)
     with torch.cuda.device(dev):
         f64 = dict(dtype=torch.float64, device=dev)
@@ -607,12 +574,7 @@ def ensemble_season(values: torch.Tensor, n_samples: int, batch: int, season: Se
     if quant is not None:
         out.peak_quantiles, out.total_quantiles = quant[0], quant[1]
     if yt is not None:
-        for k, name in enumerate(SEASON_SCORES):
-            if name == "onset_skill" and base is None:
-                continue
-            skill = name.endswith("_skill")
-            setattr(out, name, overall[k].exp() if skill else overall[k])
-            setattr(out, name + "_r", region[k].exp() if skill else region[k])
+        _set_season_scores(out, overall, region, base is not None)
     return out
 
 

@@ -1,4 +1,5 @@
-"""Shared pieces of the forecast tests (test_forecast.py, test_forecast_gpu.py)."""
+"""Shared pieces of the forecast tests (test_forecast*.py; forecast_verify_helpers.py and
+forecast_season_helpers.py build on them)."""
 import numpy as np
 import torch
 
@@ -6,6 +7,8 @@ from helpers import normwise_rel
 
 FORECAST_CASES = ["e2e_forecast_us", "e2e_forecast_state49", "e2e_forecast_us_bayes"]
 QUANTITIES = ("mean", "std", "quantiles", "nll", "skill", "mae")
+MASS_FLOOR = 4.5399929762484854e-05      # e^-10, written out: the references do not import the implementation's
+LEVELS = [0.0, 0.025, 0.5, 0.9, 1.0]
 
 
 def build_vae(g, device):
@@ -49,6 +52,31 @@ def run_forecast(g, device, monkeypatch, **kw):
     finally:
         monkeypatch.undo()
     return model, fc
+
+
+def passthrough(g, device, monkeypatch, **forecast_kw):
+    """VAE.forecast(..., **forecast_kw): (what it hands to ensemble_summary -- ``yhat``, ``S``, ``B`` and the
+    keywords under their names --, the Forecast)."""
+    from ude_amd import forecast as fmod
+    seen = {}
+    inner = fmod.ensemble_summary
+
+    def spy(yhat, n_samples, batch, **kw):
+        seen.update(kw, yhat=yhat.detach().float().cpu().numpy(), S=n_samples, B=batch)
+        return inner(yhat, n_samples, batch, **kw)
+
+    monkeypatch.setattr(fmod, "ensemble_summary", spy)
+    _, fc = run_forecast(g, device, monkeypatch, **forecast_kw)
+    return seen, fc
+
+
+def same_bits(a, b):
+    """torch.equal on the bit patterns (a NaN, as the Gaussian scores of an S = 1 group, equals itself);
+    None only equals None."""
+    if a is None or b is None:
+        return a is None and b is None
+    return a.dtype == b.dtype == torch.float64 and a.shape == b.shape and \
+        torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
 
 
 def check_against_fixture(g, fc):

@@ -10,10 +10,9 @@ import numpy as np
 import torch
 
 from helpers import normwise_rel
-from forecast_helpers import run_forecast, synth
+import forecast_helpers
+from forecast_helpers import LEVELS, MASS_FLOOR, same_bits, synth  # noqa: F401 (the tests import them here)
 
-MASS_FLOOR = 4.5399929762484854e-05
-LEVELS = [0.0, 0.025, 0.5, 0.9, 1.0]
 CONTINUOUS = ("peak_mean", "peak_std", "total_mean", "total_std", "total_quantiles", "peak_crps", "total_crps",
               "peak_crps_r", "total_crps_r")
 LOGS = ("peak_time_skill", "onset_skill", "peak_value_skill", "peak_time_skill_r", "onset_skill_r",
@@ -175,13 +174,6 @@ def check(st, ref, label=""):
         assert ok, (k, got[k], ref[k])
 
 
-def same_bits(a, b):
-    if a is None or b is None:
-        return a is None and b is None
-    return a.dtype == b.dtype == torch.float64 and a.shape == b.shape and \
-        torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
-
-
 def season_of(name):
     from ude_amd.forecast import Season
     _, _, _, _, _, base, (start, every, run, window) = case_inputs(name)
@@ -203,14 +195,4 @@ def golden_baseline(g):
 
 def passthrough(g, device, monkeypatch, season):
     """VAE.forecast(..., season=season): (the y_hat it hands to ensemble_summary, the Forecast)."""
-    from ude_amd import forecast as fmod
-    seen = {}
-    inner = fmod.ensemble_summary
-
-    def spy(yhat, n_samples, batch, **kw):
-        seen["yhat"], seen["S"], seen["B"] = yhat.detach().float().cpu().numpy(), n_samples, batch
-        return inner(yhat, n_samples, batch, **kw)
-
-    monkeypatch.setattr(fmod, "ensemble_summary", spy)
-    _, fc = run_forecast(g, device, monkeypatch, season=season)
-    return seen, fc
+    return forecast_helpers.passthrough(g, device, monkeypatch, season=season)

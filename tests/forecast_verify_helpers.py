@@ -9,11 +9,10 @@ import torch
 from scipy.stats import norm
 
 from helpers import normwise_rel
-from forecast_helpers import run_forecast, synth
+import forecast_helpers
+from forecast_helpers import LEVELS, MASS_FLOOR, same_bits, synth  # noqa: F401 (same_bits: the tests import it here)
 
-MASS_FLOOR = 4.5399929762484854e-05
 FLUSIGHT_ALPHAS = (0.02, 0.05, 0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 0.8, 0.9)
-LEVELS = [0.0, 0.025, 0.5, 0.9, 1.0]
 CONTINUOUS = ("crps", "wis", "crps_r", "wis_r", "nll_r", "mae_r")
 LOGS = ("ens_skill", "ens_skill_r", "skill_r")
 EXACT = ("coverage", "coverage_r", "pit")
@@ -114,13 +113,6 @@ def check(fc, ref, label=""):
         assert ok, (k, got[k], ref[k])
 
 
-def same_bits(a, b):
-    """torch.equal on the bit patterns (a NaN, as the Gaussian scores of an S = 1 group, equals itself)."""
-    if a is None or b is None:
-        return a is None and b is None
-    return a.dtype == b.dtype == torch.float64 and torch.equal(a.view(torch.int64), b.view(torch.int64))
-
-
 def summary(name, device="cpu", **kw):
     from ude_amd.forecast import ensemble_summary
     yhat, scale, y, S, B = case_inputs(name)
@@ -130,15 +122,6 @@ def summary(name, device="cpu", **kw):
 
 def passthrough(g, device, monkeypatch):
     """VAE.forecast(..., verify=True): (the y_hat it hands to ensemble_summary, the Forecast)."""
-    from ude_amd import forecast as fmod
-    seen = {}
-    inner = fmod.ensemble_summary
-
-    def spy(yhat, n_samples, batch, **kw):
-        seen["yhat"], seen["S"], seen["B"], seen["verify"] = yhat.detach().float().cpu().numpy(), n_samples, batch, kw["verify"]
-        return inner(yhat, n_samples, batch, **kw)
-
-    monkeypatch.setattr(fmod, "ensemble_summary", spy)
-    _, fc = run_forecast(g, device, monkeypatch, verify=True)
+    seen, fc = forecast_helpers.passthrough(g, device, monkeypatch, verify=True)
     assert seen["verify"] is True
     return seen, fc
