@@ -4,7 +4,8 @@ The library is built in-tree with hipcc (``build_prebuilt``), one object per
 model configuration of ``configs.PREBUILT`` compiled in parallel and linked
 into ``_build/libude_rk4.so``.  A configuration that is not prebuilt is
 compiled on first use into ``_build/jit/libude_rk4_<key>.so`` (same C-ABI,
-one registry entry).  There is no fallback: if no library for a model can be
+one registry entry; ``jit_prebuild`` compiles several ahead of use, side by
+side); one the kernels cannot hold is refused there with the reason.  There is no fallback: if no library for a model can be
 loaded, the fused solver raises.
 """
 from __future__ import annotations
@@ -304,7 +305,9 @@ for _cname, (_name, _types) in _CABI.items():
 def _run(cmd: List[str]) -> None:
     r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
     if r.returncode != 0:
-        raise UdeError("build command failed:\n" + " ".join(cmd) + "\n" + r.stdout[-8000:])
+        err = UdeError("build command failed:\n" + " ".join(cmd) + "\n" + r.stdout[-8000:])
+        err.output = r.stdout              # the whole log: the first error is rarely in its tail
+        raise err
 
 
 _SRC_HASH: Optional[str] = None
@@ -424,14 +427,47 @@ def prebuilt() -> NativeLib:
     return lib
 
 
-def jit_library(cfg: _cfgs.Config) -> NativeLib:
-    key = _cfgs.config_key(cfg)
-    h = source_hash()[:10]
-    path = os.path.join(JIT_DIR, f"libude_rk4_{key}_{h}.so")
+def jit_path(cfg: _cfgs.Config) -> str:
+    return os.path.join(JIT_DIR, f"libude_rk4_{_cfgs.config_key(cfg)}_{source_hash()[:10]}.so")
+
+
+_STATIC_ASSERT = re.compile(r"static assertion failed[^\n]*")
+
+
+def _jit_build(cfg: _cfgs.Config) -> str:
+    path = jit_path(cfg)
     if not os.path.exists(path):
         os.makedirs(JIT_DIR, exist_ok=True)
-        build_library([cfg], path, f"jit_{key}_{h}", jobs=1)
-    return _load(path)
+        try:
+            build_library([cfg], path, f"jit_{_cfgs.config_key(cfg)}_{source_hash()[:10]}", jobs=1)
+        except UdeError as e:
+            # a configuration the kernels cannot hold (csrc/ude_model.h's static_asserts: the record does not
+            # fit the LDS, ...) is refused here, with the compiler's reason, never at launch
+            why = sorted(set(_STATIC_ASSERT.findall(getattr(e, "output", str(e)))))
+            if why:
+                raise UdeError(f"unsupported model configuration {cfg}: " + "; ".join(why)) from e
+            raise
+    return path
+
+
+def jit_library(cfg: _cfgs.Config) -> NativeLib:
+    return _load(_jit_build(cfg))
+
+
+def jit_prebuild(cfgs: Sequence[_cfgs.Config], jobs: Optional[int] = None) -> List[str]:
+    """Build the missing JIT libraries of several configurations in parallel (at most 16 compiles at a time),
+    each at the path ``jit_library`` uses, so ``library_for`` finds them as after a first use.  Configurations
+    of ``configs.PREBUILT`` are skipped.  Returns the libraries' paths; raises the first build's ``UdeError``
+    after every build has ended."""
+    todo = [c for c in dict.fromkeys(cfgs) if c not in _cfgs.PREBUILT]
+    jobs = max(1, min(16, jobs or os.cpu_count() or 4, len(todo) or 1))
+    source_hash()                                   # read the sources once, before the threads ask
+    with ThreadPoolExecutor(max_workers=jobs) as ex:
+        futs = [ex.submit(_jit_build, c) for c in todo]
+    errs = [f.exception() for f in futs if f.exception() is not None]
+    if errs:
+        raise errs[0]
+    return [f.result() for f in futs]
 
 
 def library_for(cfg: _cfgs.Config) -> NativeLib:

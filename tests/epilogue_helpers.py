@@ -33,6 +33,12 @@ CHAIN_CASES = {
     "Fa_R1_three_steps": ("Fa", 1, 8, None, [64, 64], 4, 4, 4, 3, 0),
     "BFaFp_R1": ("BFaFp", 1, 8, [64, 64, 32], [64, 64], 6, 4, 4, 1, 0),
     "BFaFp_R10_gst": ("BFaFp", 10, 8, [64, 64, 32], [64, 64], 3, 6, 3, 1, 0),
+    # the configuration lattice (tests/lattice_helpers.py c1, c5, c7, c12): no static dims; the large-record
+    # kernels with resident weights, with the small-R paths, and with no weight residency at all
+    "lattice_c1_L3": ("Fp", 1, 3, [32, 32], None, 5, 7, 4, 1, 0),
+    "lattice_c5_R17": ("FaFp", 17, 8, [64, 64, 32], [64, 64], 5, 7, 4, 1, 0),
+    "lattice_c7_wide": ("FaFp", 1, 8, [128, 128, 128], [128, 128], 5, 7, 5, 1, 0),
+    "lattice_c12_R40": ("FaFp", 40, 8, [128, 128, 64], [128, 128], 5, 7, 3, 1, 0),
 }
 MIN_GROUP_STD = 0.015
 

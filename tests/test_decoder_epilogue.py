@@ -12,7 +12,9 @@ tests/test_bayes.py, tests/test_loss_head.py).  Every measured error is printed.
 Measured on an MI355X (normwise, against fp64; worst of the eight chain cases, the many-tiles case,
 the three consumer variants and the two recompute runs): y_hat 2.1e-7, reg 7.0e-8, nll 1.8e-7, group
 statistics 1.5e-7, rate mean / std 5.2e-8, |Fa| 5.0e-8, d y0 1.5e-6, ODE weight gradients 4.2e-6,
-d W_dec 1.8e-6, d b_dec 1.9e-6 (the largest at S = 2, at R = 49 and on the GST model).
+d W_dec 1.8e-6, d b_dec 1.9e-6 (the largest at S = 2, at R = 49 and on the GST model); the four
+configuration-lattice rows added later (tests/lattice_helpers.py) are in the table below, d b_dec 3.5e-6
+at lattice_c7_wide the largest of them.
 The same chain in torch fp32 on the host is 8e-8 .. 1.8e-6 from fp64 in d y0 and 5e-8 .. 6e-6 in the
 weight gradients on these cases, so no bar needed deriving.  nll kernels alone: nll <= 2.3e-7, group
 statistics <= 3.0e-8, d y_hat <= 1.9e-7 except 1.5e-3 at R49_T9_S2_B40 (torch fp32: 3.2e-2; some of
@@ -30,6 +32,10 @@ reference; then the kernel's errors):
   Fa_R1_three_steps   0   4.9e-3   6%   0.80  0.033  | 5.6e-8  1.1e-7  5.0e-8  3.4e-7  3.9e-7  9.4e-8  1.2e-7
   BFaFp_R1            0   2.7e-2  25%   0.78  0.026  | 3.5e-8  7.2e-8  3.3e-8  4.5e-7  3.5e-7  1.7e-7  2.1e-7
   BFaFp_R10_gst       0   5.4e-3  29%   0.72  0.023  | 1.0e-7  1.4e-7  9.3e-8  1.4e-7  2.6e-7  1.7e-6  1.9e-6
+  lattice_c1_L3       0   7.1e-2  14%   0.81  0.039  | 3.8e-8  8.1e-8  3.4e-8  3.2e-7  4.4e-7  3.5e-7  4.6e-7
+  lattice_c5_R17      0   1.2e-3  25%   0.69  0.059  | 1.5e-7  1.8e-7  1.1e-7  7.3e-8  2.1e-7  5.7e-7  5.5e-7
+  lattice_c7_wide     0   3.3e-2  14%   0.65  0.020  | 6.5e-8  9.9e-8  6.0e-8  2.8e-7  2.1e-7  8.2e-7  3.5e-6
+  lattice_c12_R40     0   1.2e-2  25%   0.72  0.030  | 2.0e-7  1.3e-7  1.4e-7  5.9e-8  2.7e-7  1.4e-6  1.4e-6
   3073 tiles / 2048   0   6.9e-2  25%   0.78  0.031  | 3.7e-8  8.5e-8  1.8e-8  5.1e-8  1.2e-7  3.0e-8  1.7e-8
 Consumer variants (FaFp_R1_two_steps): d y0 1.2e-7 / 1.4e-7 / 1.1e-7, d ode 1.2e-7 / 3.4e-7 / 5.0e-7, d W, d b
 exactly zero without a y_hat consumer, else 2.3e-7 / 1.1e-8; static dims of d y0 6.5e-8.  The recompute

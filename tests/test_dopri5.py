@@ -76,21 +76,21 @@ def test_oracle_dense_output_matches_step_ends():
     assert torch.allclose(sol_a[-1], sol_b[-1], rtol=1e-12, atol=1e-14)
 
 
-def _module(pkg, kind, R, net, aug, seed=0):
+def _module(pkg, kind, R, net, aug, seed=0, L=8):
     torch.manual_seed(seed)
     kw = {}
     if net is not None:
         kw["net_sizes"] = net
     if aug is not None:
         kw["aug_net_sizes"] = aug
-    return getattr(pkg, kind)(R, latent_dim=8, **kw)
+    return getattr(pkg, kind)(R, latent_dim=L, **kw)
 
 
-def _y0(N, R, seed=1):
+def _y0(N, R, seed=1, L=8):
     gen = torch.Generator().manual_seed(seed)
     S = torch.rand(N, R, generator=gen) * 0.4 + 0.5
     I = torch.rand(N, R, generator=gen) * 0.05
-    return torch.cat([S[..., None], I[..., None], (1 - S - I)[..., None], torch.randn(N, R, 5, generator=gen)], -1) \
+    return torch.cat([S[..., None], I[..., None], (1 - S - I)[..., None], torch.randn(N, R, L - 3, generator=gen)], -1) \
         + 1e-5
 
 
@@ -252,6 +252,10 @@ CASES = [
     ("Fa", 1, None, [64, 64], 17, 6, 7.0, 1e-6, 1e-8),
     ("FaFp", 10, [64, 64, 32], [64, 64], 40, 5, 5.0, 1e-6, 1e-8),
     ("FaFp", 49, [64, 64, 32], [64, 64], 24, 3, 2.0, 1e-6, 1e-8),
+    # the configuration lattice (tests/lattice_helpers.py c1, c5, c7; a tenth entry is the latent dim)
+    ("Fp", 1, [32, 32], None, 37, 5, 7.0, 1e-6, 1e-8, 3),
+    ("FaFp", 17, [64, 64, 32], [64, 64], 37, 5, 7.0, 1e-6, 1e-8),
+    ("FaFp", 1, [128, 128, 128], [128, 128], 37, 5, 7.0, 1e-6, 1e-8),
 ]
 # Horizons stop before the random-weight models drive a state across the [-1, 2]
 # mask (lib/models.py:130): the RHS is discontinuous there, the controller rejects
@@ -262,11 +266,12 @@ CASES = [
 @pytest.mark.gpu
 @pytest.mark.parametrize("case", CASES, ids=lambda c: f"{c[0]}_R{c[1]}_N{c[4]}_T{c[5]}_rtol{c[7]:g}")
 def test_fused_dopri5_matches_oracle(pkg, case):
-    kind, R, net, aug, N, T, div, rtol, atol = case
-    mod = _module(pkg, kind, R, net, aug)
+    kind, R, net, aug, N, T, div, rtol, atol = case[:9]
+    L = case[9] if len(case) > 9 else 8
+    mod = _module(pkg, kind, R, net, aug, L=L)
     if kind == "FaFp":
         mod.Fa_w = 0.8
-    y0 = _y0(N, R)
+    y0 = _y0(N, R, L=L)
     t = torch.arange(T, dtype=torch.float32) / div
     rhs32 = OracleRHS.from_module(mod, torch.float32)
     st32 = Dopri5Stats()

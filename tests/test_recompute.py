@@ -10,6 +10,7 @@ import pytest
 import torch
 
 from helpers import normwise_rel
+from lattice_helpers import split_bwd
 from oracle.ude_oracle import OracleRHS, solve_and_grad
 
 pytestmark = pytest.mark.gpu
@@ -67,9 +68,11 @@ def test_recompute_bit_identical_and_vs_oracle(pkg, case):
     assert b[0] == 1 and b[1] == 0, "a zero budget selects the recompute path"
     assert torch.equal(a[2], b[2]) and torch.equal(a[3], b[3]), "latent / dy0 differ"
     # weight gradients: bit-identical where both backwards accumulate them the same way (R = 49);
-    # small records' stored path is the 8-wave split kernel, whose partner waves sum the bias rows
-    # per trajectory first (a different fp32 summation order than the 4-wave recompute kernel)
-    split = R <= 16
+    # small records' stored path is the 8-wave split kernel (Model::SPLIT_BWD, read from ude_model.h's own
+    # printed traits), whose partner waves sum the bias rows per trajectory first (a different fp32
+    # summation order than the 4-wave recompute kernel)
+    from ude_amd import configs
+    split = split_bwd(configs._c(kind, R, 8, net, aug))
     for ga, gb in zip(a[4], b[4]):
         if split:
             assert normwise_rel(gb, ga) < 1e-6
