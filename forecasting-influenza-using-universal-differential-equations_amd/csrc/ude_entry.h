@@ -10,6 +10,10 @@
 //    forecast_dec that validates, fills the KArgs fields only it has, and calls launch_forward.
 //  - a persistent kernel's grid: occupancy_grid.
 //  - a change to the right-hand side: ude_sir.h, and the oracle restatements.
+//  - a change to a kernel: ude_kernels.h is the umbrella over the RK4 kernels' parts -- ude_kernels_core.h
+//    (wrappers, KArgs, indexing, statistics), _mlp.h (the layer GEMMs forward and backward), _fwd.h and
+//    _bwd.h (the solve bodies and their kernels), _pack.h (weight packing), _tail.h (reductions behind the
+//    backward); the other solves are ude_dopri5.h, ude_eval.h, ude_gst.h and ude_loss.h.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdlib.h>
@@ -57,6 +61,11 @@ inline int occupancy_grid(const void* kernel, int threads, size_t lds, int devic
   if (cus_out) *cus_out = cus;
   return UDE_OK;
 }
+
+// trajectory tiles of a problem (TT trajectories each, the last one ragged)
+inline int n_tiles_of(const UdeProblem* p) { return (p->n_traj + TT - 1) / TT; }
+// workspace sections start on 256-byte boundaries
+inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 template <class M> struct is_recompute { static constexpr bool value = false; };
 template <class B> struct is_recompute<Recompute<B>> { static constexpr bool value = true; };
@@ -139,8 +148,6 @@ struct Ops {
     done = true;
     return UDE_OK;
   }
-
-  static int n_tiles_of(const UdeProblem* p) { return (p->n_traj + TT - 1) / TT; }
 
   // forward grid (the plain training kernel's occupancy; stats_slab / reg_slab are sized by it) and
   // backward grid; cus: the device's CU count, for the callers that need it as well
@@ -359,7 +366,7 @@ struct Ops {
     if (p->n_steps < 1 || p->n_out + 1 > DecBwdDims<M>::MAX_T) return UDE_E_INVALID;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int gd = 1;
     int rc = dec_grid(dev, n_tiles, &gd);
     if (rc) return rc;
@@ -379,7 +386,7 @@ struct Ops {
 
   // nll_loss over y_hat: ws = musd (T, B, R, 2) floats | per-block fp64 partials
   static int64_t nll_blocks(int T, int B) { return ((int64_t)T * B * M::R + 255) / 256; }
-  static int64_t nll_part_off(int T, int B) { return (((int64_t)T * B * M::R * 2 * 4) + 255) & ~(int64_t)255; }
+  static int64_t nll_part_off(int T, int B) { return (int64_t)align256((size_t)T * B * M::R * 2 * 4); }
   static int nll_workspace(int T, int S, int B, int64_t* bytes) {
     if (T < 1 || S < 2 || B < 1) return UDE_E_INVALID;
     *bytes = nll_part_off(T, B) + nll_blocks(T, B) * 8;
@@ -618,21 +625,20 @@ struct DopriOps {
   }
 
   static Layout layout(int n_tiles, int grid) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     Layout L;
     L.ctl = 0;
-    L.part = al(sizeof(DopriCtl));
-    L.stats = L.part + al((size_t)grid * 4 * 8);
-    L.S = L.stats + al((size_t)grid * 5 * 8);
-    L.Cm = L.S + al((size_t)2 * n_tiles * 2 * M::F * TT * 4);
-    L.total = L.Cm + al((size_t)n_tiles * M::F * TT * 4);
+    L.part = align256(sizeof(DopriCtl));
+    L.stats = L.part + align256((size_t)grid * 4 * 8);
+    L.S = L.stats + align256((size_t)grid * 5 * 8);
+    L.Cm = L.S + align256((size_t)2 * n_tiles * 2 * M::F * TT * 4);
+    L.total = L.Cm + align256((size_t)n_tiles * M::F * TT * 4);
     return L;
   }
 
   static int workspace(const UdeProblem* p, int device, int64_t* bytes) {
     if (M::BAYES) return UDE_E_UNSUPPORTED;
     if (p->n_traj < 1 || p->n_out < 0) return UDE_E_INVALID;
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int grid = 1;
     int rc = attrs_grid(device, n_tiles, &grid);
     if (rc) return rc;
@@ -648,7 +654,7 @@ struct DopriOps {
     if (max_steps < 1) max_steps = 1;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int grid = 1;
     int rc = attrs_grid(dev, n_tiles, &grid);
     if (rc) return rc;
@@ -726,12 +732,11 @@ struct LossOps {
     return occupancy_grid(k, LTHREADS, lds, device, (long)T * B, g);
   }
   static Layout layout(int T, int B, int gf, int gb) {
-    auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
     Layout L;
     L.musd = 0;
-    L.part = al((size_t)T * B * M::R * 2 * 4);
-    L.slab = L.part + al((size_t)gf * 2 * 8);
-    L.total = L.slab + al((size_t)gb * D::SLAB * 4);
+    L.part = align256((size_t)T * B * M::R * 2 * 4);
+    L.slab = L.part + align256((size_t)gf * 2 * 8);
+    L.total = L.slab + align256((size_t)gb * D::SLAB * 4);
     return L;
   }
   static int grids(int device, int T, int S, int B, int* gf, int* gb) {
@@ -818,7 +823,7 @@ struct EvalOps {
   static int workspace(const UdeProblem* p, int device, int64_t* bytes) {
     if (M::BAYES) return UDE_E_UNSUPPORTED;      // each evaluation's sample is a deterministic RHS
     if (p->n_traj < 1) return UDE_E_INVALID;
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int gf = 1, gb = 1;
     int rc = grids(device, n_tiles, &gf, &gb);
     if (rc) return rc;
@@ -833,7 +838,7 @@ struct EvalOps {
     if (!pack || !x || !f || p->n_traj < 1) return UDE_E_INVALID;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int gf = 1, gb = 1;
     int rc = grids(dev, n_tiles, &gf, &gb);
     if (rc) return rc;
@@ -865,7 +870,7 @@ struct EvalOps {
     if (!pack || !x || !cot_f || !dx || !ws || !dparams || p->n_traj < 1) return UDE_E_INVALID;
     int dev = 0;
     HIPCHK(hipGetDevice(&dev));
-    const int n_tiles = (p->n_traj + TT - 1) / TT;
+    const int n_tiles = n_tiles_of(p);
     int gf = 1, gb = 1;
     int rc = grids(dev, n_tiles, &gf, &gb);
     if (rc) return rc;
