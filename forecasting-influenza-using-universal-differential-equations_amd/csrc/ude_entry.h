@@ -80,21 +80,35 @@ struct Ops {
   static_assert(!M::HOIST || DY0_STATIC_LDS <= 160 * 1024, "dy0 static time sums do not fit the 160 KiB LDS");
 
   // ---- the forward kernel's variants ---------------------------------------------------------------
-  // One row per ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN> this model has:
+  // One row per ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN, SCN> this model has:
   //   train: stores the training checkpoint;  dec: the decoder epilogue (y_hat, no latent);
   //   split: the 8-wave kernel (Model::SPLIT_FWD);  res: resident weights, one workgroup per CU
-  //   (Model::FWD_RES);  dyn: the dynamics channels beside y_hat (inference dec, deterministic weights).
+  //   (Model::FWD_RES);  dyn: the dynamics channels beside y_hat (inference dec, deterministic weights);
+  //   scn: a scenario table scales the rates (inference dec, deterministic weights, a rate net; with or
+  //   without dyn).
   // fwd_variant calls f(kernel, threads, dynamic LDS bytes) for the row of the given facts and returns
   // f's result, or NO_VARIANT when the model has no such kernel.  Inference with the decoder epilogue
   // (the forecast) stores nothing, so the Recompute view has none.
   static constexpr int NO_VARIANT = 1;
-  template <bool TRAIN, bool DEC, bool SPLIT, bool RES, bool DYN = false, class F>
+  template <bool TRAIN, bool DEC, bool SPLIT, bool RES, bool DYN = false, bool SCN = false, class F>
   static int fwd_row(F&& f) {
-    return f((const void*)&ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN>, SPLIT ? 2 * NTHREADS : NTHREADS,
+    return f((const void*)&ude_fwd_kernel<M, TRAIN, SPLIT, DEC, RES, DYN, SCN>, SPLIT ? 2 * NTHREADS : NTHREADS,
              DEC ? M::LDS_F_DEC : M::LDS_F);
   }
   template <class F>
-  static int fwd_variant(bool train, bool dec, bool split, bool res, bool dyn, F&& f) {
+  static int fwd_variant(bool train, bool dec, bool split, bool res, bool dyn, bool scn, F&& f) {
+    if (scn) {
+      // a scenario: inference dec x {plain, res} x {dyn, no dyn}; deterministic weights, a rate net
+      if constexpr (!is_recompute<M>::value && !M::BAYES && M::HAS_P) {
+        if (!train && dec && !split && !res)
+          return dyn ? fwd_row<false, true, false, false, true, true>(f) : fwd_row<false, true, false, false, false, true>(f);
+        if constexpr (M::FWD_RES) {
+          if (!train && dec && !split && res)
+            return dyn ? fwd_row<false, true, false, true, true, true>(f) : fwd_row<false, true, false, true, false, true>(f);
+        }
+      }
+      return NO_VARIANT;
+    }
     if (dyn) {
       if constexpr (!is_recompute<M>::value && !M::BAYES) {
         if (!train && dec && !split && !res) return fwd_row<false, true, false, false, true>(f);
@@ -130,8 +144,8 @@ struct Ops {
     static bool done = false;
     if (done) return UDE_OK;
     // record + (when it fits) the schedule: up to the full 160 KiB, for every forward variant there is
-    for (int v = 0; v < 32; ++v) {
-      const int rc = fwd_variant(v & 1, v & 2, v & 4, v & 8, v & 16, [](const void* k, int, int) -> int {
+    for (int v = 0; v < 64; ++v) {
+      const int rc = fwd_variant(v & 1, v & 2, v & 4, v & 8, v & 16, v & 32, [](const void* k, int, int) -> int {
         HIPCHK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, LDS_MAX));
         return UDE_OK;
       });
@@ -154,7 +168,7 @@ struct Ops {
   static int grid_fwd(int device, int n_tiles, int* gf, int* cus = nullptr) {
     int rc = ensure_attrs();
     if (rc) return rc;
-    return fwd_variant(true, false, false, false, false, [&](const void* k, int threads, int lds) {
+    return fwd_variant(true, false, false, false, false, false, [&](const void* k, int threads, int lds) {
       return occupancy_grid(k, threads, lds, device, n_tiles, gf, cus);
     });
   }
@@ -355,6 +369,26 @@ struct Ops {
     }
   }
 
+  // The forecast under a scenario: forecast_dec's solve with the rates scaled by scn (n_steps, R, 2), fp32,
+  // 8-byte aligned: scn[k][r] = (m_beta, m_gamma) of region r in RK4 step k, all four stages of the step
+  // (fwd_body, SCN).  dyn is nullable: with it the channels of forecast_dyn, beta / gamma / r_eff those of
+  // the scaled rates.  The side statistics are the scaled rates'.  A model without a rate net has nothing
+  // to scale; Bayesian and recompute models have no such kernel.
+  static int forecast_scn(const UdeProblem* p, const float* pack, const void* sched, const float* y0,
+                          const float* dec_pack, const float* scn, float* yhat, float* dyn, double* stats_slab,
+                          const UdeSideStats* st, unsigned* ctl, hipStream_t s) {
+    if constexpr (is_recompute<M>::value || M::BAYES || !M::HAS_P) {
+      return UDE_E_UNSUPPORTED;
+    } else {
+    if (!pack || !sched || !y0 || !dec_pack || !scn || !yhat || !stats_slab || !stats_ok(st)) return UDE_E_INVALID;
+    if (p->n_steps < 1 || (reinterpret_cast<uintptr_t>(scn) & 7)) return UDE_E_INVALID;
+    KArgs a;
+    memset(&a, 0, sizeof(a));
+    a.dec_pack = dec_pack; a.yhat = yhat; a.dyn = dyn; a.scn = scn;
+    return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
+    }
+  }
+
   // Backward of the decoder epilogue: dl3 (T, N, R, 3) for ude_rk4_backward_sir, d W_dec, d b_dec.
   static int dec_backward(const UdeProblem* p, const void* sched, const float* ckpt, const float* dyhat,
                           const float* W, const float* grad_reg, void* ws, float* dl3, float* dW, float* db,
@@ -501,10 +535,11 @@ struct Ops {
     return launch_forward(p, pack, sched, y0, stats_slab, st, ctl, a, s);
   }
 
-  // The one forward launch behind forward / forward_dec / forecast_dec / forecast_dyn.  `a` arrives zeroed
-  // except for what only its entry has (outputs, checkpoint, decoder pack); a.ckpt says whether the solve
-  // stores the training checkpoint, a.yhat whether it runs the decoder epilogue, a.dyn whether it emits the
-  // dynamics channels.  Kernel selection:
+  // The one forward launch behind forward / forward_dec / forecast_dec / forecast_dyn / forecast_scn.  `a`
+  // arrives zeroed except for what only its entry has (outputs, checkpoint, decoder pack, scenario table);
+  // a.ckpt says whether the solve stores the training checkpoint, a.yhat whether it runs the decoder
+  // epilogue, a.dyn whether it emits the dynamics channels, a.scn whether a scenario scales the rates.
+  // Kernel selection:
   //   split    iff it stores a checkpoint, the model has the 8-wave kernel and every tile has a CU of
   //            its own (so an inference solve, the forecast included, never splits);
   //   resident else iff fwd_res(): one workgroup per CU, gf = min(n_tiles, cus) (<= the slabs' size);
@@ -529,7 +564,7 @@ struct Ops {
     const bool split = train && M::SPLIT_FWD && n_tiles <= cus;
     const bool res = !split && fwd_res(n_tiles, cus);
     if (res) gf = n_tiles < cus ? n_tiles : cus;
-    rc = fwd_variant(train, dec, split, res, a.dyn != nullptr, [&](const void* k, int threads, int lds) -> int {
+    rc = fwd_variant(train, dec, split, res, a.dyn != nullptr, a.scn != nullptr, [&](const void* k, int threads, int lds) -> int {
       void* args[] = {&a};
       HIPCHK(hipLaunchKernel(k, dim3(gf), dim3(threads), args, lds, s));
       return UDE_OK;
@@ -935,6 +970,8 @@ struct Entry {
                       double*, const UdeSideStats*, unsigned*, float*, hipStream_t);
   int (*forecast_dyn)(const UdeProblem*, const float*, const void*, const float*, const float*, float*, float*,
                       double*, const UdeSideStats*, unsigned*, hipStream_t);
+  int (*forecast_scn)(const UdeProblem*, const float*, const void*, const float*, const float*, const float*, float*,
+                      float*, double*, const UdeSideStats*, unsigned*, hipStream_t);
 };
 
 template <class M>
@@ -944,7 +981,7 @@ constexpr Entry make_entry() {
                &LossOps<M>::backward, &LossOps<M>::backward_sir, &EvalOps<M>::workspace, &EvalOps<M>::forward,
                &EvalOps<M>::vjp, &Ops<M>::dec_pack, &Ops<M>::forward_dec, &Ops<M>::dec_backward,
                &Ops<M>::nll_workspace, &Ops<M>::nll_forward, &Ops<M>::nll_backward, &EvalOps<M>::fused,
-               &Ops<M>::forecast_dec, &Ops<M>::forecast_dyn};
+               &Ops<M>::forecast_dec, &Ops<M>::forecast_dyn, &Ops<M>::forecast_scn};
 }
 
 

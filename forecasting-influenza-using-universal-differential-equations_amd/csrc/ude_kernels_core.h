@@ -78,6 +78,7 @@ struct KArgs {
   float* o_reg;               // DEC: latent_init_loss (1 float)
   double n_eval;              // 4 n_steps N R: the number of recorded rates per statistic
   float* dyn;                 // DYN forward: (C, T, N, R) dynamics channels (dyn_channels<M>() of them)
+  const float* scn;           // SCN forward: (n_steps, R, 2) multipliers of (beta, gamma) per step and region
 };
 
 // The channels of the DYN forward, in order: s, i, r; beta, gamma, r_eff (rate net); fa_s, fa_i, fa_r
@@ -173,6 +174,15 @@ __device__ __forceinline__ Rsrc make_rsrc(const float* p, int bytes) {
 }
 __device__ __forceinline__ f4 ldw(Rsrc rs, int voff_bytes, int soff_bytes) {
   return __builtin_bit_cast(f4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff_bytes, soff_bytes, 0));
+}
+
+// SCN: the scenario's multipliers (m_beta, m_gamma) of region r in the step whose row starts row_bytes into
+// the (n_steps, R, 2) table: one 8-byte load through a buffer resource (no 64-bit lane address).  The row
+// offset is wave-uniform; the callers keep r < R and the row below n_steps (the table is 8-byte aligned:
+// the host entry checks).
+typedef float f2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ f2 ld_scn(Rsrc rs, int r, int row_bytes) {
+  return __builtin_bit_cast(f2, __builtin_amdgcn_raw_buffer_load_b64(rs, r * 8, row_bytes, 0));
 }
 
 __device__ __forceinline__ size_t ckpt_index(int tile, int n_steps, int step, int stage, int F, int f, int t) {

@@ -1,5 +1,5 @@
 // The forward solve: tile starts, fwd_body (all four RK4 stages of every step, the training stores, the DEC
-// and DYN epilogues), fwd_sbody (the split forward's store waves) and ude_fwd_kernel.
+// and DYN epilogues, the SCN rate multipliers), fwd_sbody (the split forward's store waves) and ude_fwd_kernel.
 #pragma once
 #include "ude_kernels_mlp.h"
 
@@ -113,9 +113,22 @@ __device__ __forceinline__ void store_ckpt_rows(float* blk, const float* lds, in
 // last output time ends the last step and has no evaluation of the solve, so one more mlp_forward runs
 // on the final state and the same pass follows it: no RK update, no store but A.dyn, nothing added to
 // the side statistics.
-template <class M, bool TRAIN, int W, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false>
+// SCN (the inference DEC forward of a deterministic model with a rate net): a scenario.  A.scn is a table
+// (n_steps, R, 2) of multipliers; all four stage evaluations of step k scale the rate net's outputs of
+// region r by row k -- beta' = |m[k][r][0] q0|, gamma' = |m[k][r][1] q1|, which for m >= 0 is fl(m |q|), so
+// a table of ones gives the plain solve's bits -- before sir_flux; Fa, the mask and the RK update are
+// unchanged, and the side statistics sum the scaled rates.  Per step, not per time: stage 4 of step k is
+// evaluated at the start time of step k + 1 and still takes row k.  With DYN the channels report the scaled
+// rates: an output that starts a step takes that step's row, the last output the last step's.
+// Each thread's pairs keep their region from step to step: their multipliers (2 SLOTS registers) are loaded
+// once per step ahead of stage 0's layers and held for its four flux passes, or at the head of every flux
+// pass where the registers are not there (SCN_AHEAD below).
+template <class M, bool TRAIN, int W, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false,
+          bool SCN = false>
 __device__ void fwd_body(const KArgs& A, float* lds) {
   static_assert(!DYN || (DEC && !TRAIN && !SPLIT && !M::BAYES), "DYN: the deterministic inference DEC forward only");
+  static_assert(!SCN || (DEC && !TRAIN && !SPLIT && !M::BAYES && M::HAS_P),
+                "SCN: the deterministic inference DEC forward of a model with a rate net only");
   constexpr int SR = M::SR_F;
   constexpr int SL = M::SLOTS;
   int tid = threadIdx.x;
@@ -124,6 +137,14 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
   const size_t NRL = (size_t)A.n_traj * M::R * M::L;
   const Rsrc rs = make_rsrc(A.pack, M::PACK_TOTAL * 4);
   const Rsrc rsd = DEC ? make_rsrc(A.dec_pack, M::DEC_PACK * 4) : rs;
+  constexpr int SCN_ROW = M::R * 8;              // bytes of one step's row of the scenario table
+  // where the plain kernel streams its weights (!WREG) there is room to hold a step's multipliers of the
+  // thread's pairs from ahead of stage 0's layers (state49 FaFp: 213 -> 221 VGPRs, no scratch; forecast_scn
+  // 2.116 ms against 2.162 ms with the loads in the flux pass, forecast_dec 2.113 - 2.133); a model whose
+  // fragments live in registers is at its limit (state49 Fp: 256 VGPRs and 32 B of scratch without SCN):
+  // its loads go at the head of every flux pass (24 B of scratch; held across the step: 40 B)
+  constexpr bool SCN_AHEAD = !M::WREG;
+  const Rsrc rsm = SCN ? make_rsrc(A.scn, A.n_steps * SCN_ROW) : rs;
   double st_b = 0, st_g = 0, st_bb = 0, st_gg = 0, st_fa = 0;
   // DEC: this thread's latent_init_loss partial lives in LDS behind the record (the large models'
   // forward is at its 256-VGPR limit: two more live registers spilled)
@@ -190,7 +211,7 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
     // formed here per use, not hoisted into registers the stage loop needs (at R = 49 the plain kernel is
     // close to its 256 VGPRs).  4-B stores at stride R across the tile's trajectories, as the latent
     // stores of the models without 16-B rows.
-    auto dyn_pass = [&](int jo) {
+    auto dyn_pass = [&](int jo, [[maybe_unused]] int row) {
       if constexpr (DYN) {
         int td = threadIdx.x;
         asm volatile("" : "+v"(td));
@@ -208,7 +229,12 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             dst[2 * CS] = rec[M::Y_OFF + 3 * r + 2];
             if constexpr (M::HAS_P) {
               float b, gm;
-              sir_rates(rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], b, gm);
+              if constexpr (SCN) {
+                const f2 m = ld_scn(rsm, r, row * SCN_ROW);
+                sir_rates(m[0] * rec[Q_OUT<M> + 2 * r], m[1] * rec[Q_OUT<M> + 2 * r + 1], b, gm);
+              } else {
+                sir_rates(rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], b, gm);
+              }
               dst[3 * CS] = b;
               dst[4 * CS] = gm;
               dst[5 * CS] = sir_r_eff(b, s, gm);
@@ -302,6 +328,15 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
         if (step == 0) dyn_jo = 0;
         else if (sc.out_start[step - 1] < sc.out_start[step]) dyn_jo = sc.out_j[sc.out_start[step - 1]];
       }
+      // SCN: this step's multipliers of the thread's pairs, in flight under stage 0's layers ...
+      [[maybe_unused]] f2 mq[SL];
+      if constexpr (SCN && SCN_AHEAD) {
+        sfor<SL>([&](auto ss) {
+          constexpr int sl = decltype(ss)::value;
+          const int p = tid + sl * NTHREADS;
+          mq[sl] = ld_scn(rsm, min(p / TT, M::R - 1), step * SCN_ROW);      // p >= PAIRS: a valid row entry, unused
+        });
+      }
       for (int j = 0; j < 4; ++j) {
         // BAYES: evaluation 4 step + j has its own weight sample
         Rsrc rse = rs;
@@ -344,7 +379,14 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
         }
         UDE_STAMP(pf, 0);
         if constexpr (DYN) {
-          if (j == 0 && dyn_jo >= 0) dyn_pass(dyn_jo);
+          if (j == 0 && dyn_jo >= 0) dyn_pass(dyn_jo, step);
+        }
+        if constexpr (SCN && !SCN_AHEAD) {                   // ... or loaded here, every stage
+          sfor<SL>([&](auto ss) {
+            constexpr int sl = decltype(ss)::value;
+            const int p = tid + sl * NTHREADS;
+            mq[sl] = ld_scn(rsm, min(p / TT, M::R - 1), step * SCN_ROW);
+          });
         }
         if constexpr (UDE_ABL != 12) sfor<SL>([&](auto ss) {
           constexpr int sl = decltype(ss)::value;
@@ -368,7 +410,10 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             }
             if constexpr (M::HAS_P) {
               float b, gm;
-              sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
+              if constexpr (SCN)
+                sir_flux(Y[0], Y[1], mq[sl][0] * rec[Q_OUT<M> + 2 * r], mq[sl][1] * rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
+              else
+                sir_flux(Y[0], Y[1], rec[Q_OUT<M> + 2 * r], rec[Q_OUT<M> + 2 * r + 1], f, b, gm);
               if (valid && UDE_ABL != 14) {
                 st_b += (double)b; st_g += (double)gm;
                 st_bb += (double)b * (double)b; st_gg += (double)gm * (double)gm;
@@ -480,7 +525,7 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
       if (sc.out_start[last] < sc.out_start[last + 1]) {
         const int jo = sc.out_j[sc.out_start[last]];
         mlp_forward<M, W, SR>(rs, lds, c1, lane, wr, pf);
-        dyn_pass(jo);
+        dyn_pass(jo, last);                      // SCN: the last step's row
         lds_sync();
       }
     }
@@ -557,17 +602,19 @@ __device__ void fwd_sbody(const KArgs& A, float* lds) {
 // SPLIT (training, Model::split_fwd, launched when every tile has a CU of its own): 8 waves.
 // DEC: the decoder epilogue (y_hat and latent_init_loss, no latent).
 // DYN: the dynamics channels beside y_hat (the deterministic inference DEC forward only; see fwd_body).
-template <class M, bool TRAIN, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false>
+// SCN: a scenario table scales the rates per step and region (the same forward only; see fwd_body).
+template <class M, bool TRAIN, bool SPLIT = false, bool DEC = false, bool RES = false, bool DYN = false,
+          bool SCN = false>
 __global__ __launch_bounds__(SPLIT ? 2 * NTHREADS : NTHREADS, (SPLIT || RES) ? 1 : 2) void ude_fwd_kernel(KArgs a) {
   extern __shared__ __attribute__((aligned(16))) float lds[];
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   if constexpr (SPLIT) {
     if (w >= WAVES) { fwd_sbody<M, DEC>(a, lds); return; }
   }
-  if (w == 0) fwd_body<M, TRAIN, 0, SPLIT, DEC, RES, DYN>(a, lds);
-  else if (w == 1) fwd_body<M, TRAIN, 1, SPLIT, DEC, RES, DYN>(a, lds);
-  else if (w == 2) fwd_body<M, TRAIN, 2, SPLIT, DEC, RES, DYN>(a, lds);
-  else fwd_body<M, TRAIN, 3, SPLIT, DEC, RES, DYN>(a, lds);
+  if (w == 0) fwd_body<M, TRAIN, 0, SPLIT, DEC, RES, DYN, SCN>(a, lds);
+  else if (w == 1) fwd_body<M, TRAIN, 1, SPLIT, DEC, RES, DYN, SCN>(a, lds);
+  else if (w == 2) fwd_body<M, TRAIN, 2, SPLIT, DEC, RES, DYN, SCN>(a, lds);
+  else fwd_body<M, TRAIN, 3, SPLIT, DEC, RES, DYN, SCN>(a, lds);
 }
 
 }  // namespace ude

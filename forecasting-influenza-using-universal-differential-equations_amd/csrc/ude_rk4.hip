@@ -305,6 +305,15 @@ int ude_rk4_forecast_dyn(const UdeModelDesc* m, const UdeProblem* p, const float
   return e->forecast_dyn(p, pack, sched, y0, dec_pack, yhat, dyn, stats_slab, stats, ctl, (hipStream_t)stream);
 }
 
+int ude_rk4_forecast_scn(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,
+                         const float* y0, const float* dec_pack, const float* scn, float* yhat, float* dyn,
+                         double* stats_slab, uint32_t* ctl, const UdeSideStats* stats, ude_stream_t stream) {
+  const Entry* e = find(m);
+  if (!e) return UDE_E_UNSUPPORTED;
+  if (!p || p->n_traj < 1 || p->n_steps < 1 || !stats || !scn) return UDE_E_INVALID;
+  return e->forecast_scn(p, pack, sched, y0, dec_pack, scn, yhat, dyn, stats_slab, stats, ctl, (hipStream_t)stream);
+}
+
 int ude_forecast_summary_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t n_q, int64_t* ws_bytes) {
   return ude::forecast_summary_workspace(T, S, B, R, n_q, ws_bytes);
 }

@@ -211,7 +211,7 @@ class VAE:
         return y_pred
 
     def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False,
-                 season=None):
+                 season=None, scenarios=None):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
@@ -238,7 +238,29 @@ class VAE:
         distribution of each trajectory's peak value, peak time, total and (with a baseline) onset, and
         with targets their scores against the observed season, from the same prediction on every route
         (ude_forecast_season on the device: the prediction is still not copied to the host).  With
-        ``season=None`` nothing changes."""
+        ``season=None`` nothing changes.
+
+        ``scenarios`` -- a mapping name -> ``ude_amd.forecast.Scenario`` (multipliers of beta and gamma per
+        output interval and region) -- also fills ``Forecast.scenarios[name]`` with a
+        ``ude_amd.forecast.ScenarioForecast``.  The draw, the baseline solve and its summaries are exactly
+        those of the call without it; every scenario is then solved on the same ``z`` (on the fused path by
+        ude_rk4_forecast_scn, still without a latent; otherwise on the module's layers,
+        ``ude_amd.forecast.scenario_latent``), so ``effect`` -- the summary of the paired difference
+        scenario - baseline -- carries no sampling noise of its own.  A scenario's side statistics are
+        returned in ``rates`` and never recorded on the RHS.  An RHS without a rate net (Fa) or a Bayesian
+        one raises ValueError."""
+        if scenarios is not None:
+            scenarios = dict(scenarios)
+            for name, sc in scenarios.items():
+                if not isinstance(sc, ude_forecast.Scenario):
+                    raise TypeError(f"forecast: scenarios[{name!r}] is not an ude_amd.forecast.Scenario")
+            if getattr(self.ode, "ode_type", None) not in ("Fp", "FaFp"):
+                raise ValueError("forecast: scenarios scale the rate net's beta and gamma; this RHS "
+                                 f"({getattr(self.ode, 'ode_type', type(self.ode).__name__)}) has no rate net")
+            if getattr(self.ode, "uncertainty", "none") == "bayes":
+                raise ValueError("forecast: scenarios of a Bayesian RHS are not supported (every evaluation "
+                                 "draws its own weights; there is no paired solve)")
+        z = None
         B = x.shape[0]
         dev_is_hip = torch.device(self.device).type == "cuda"
         lin = decoder_head.decoder_linear(self.dec)
@@ -276,6 +298,8 @@ class VAE:
                 n_samples = 1
             yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(y_pred.shape[2], n_samples * B, self.n_regions)
             dyn = ude_forecast.latent_dynamics(self.ode, self.latent) if dynamics else None
+            if scenarios:
+                z = self.latent[0]                                               # the draw: latent[0] is y0
         fc = ude_forecast.ensemble_summary(yhat, n_samples, B, y_true=y_true, scale=scaler, quantiles=quantiles,
                                            verify=verify)
         if dynamics:
@@ -283,7 +307,45 @@ class VAE:
         if season is not None:
             fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,
                                                      quantiles=quantiles)
+        if scenarios is not None:
+            fc.scenarios = {name: self._forecast_scenario(sc, z, t, yhat, n_samples, B, scaler, quantiles, dynamics,
+                                                          season) for name, sc in scenarios.items()}
         return fc
+
+    def _forecast_scenario(self, scenario, z, t, yhat, n_samples, B, scaler, quantiles, dynamics, season):
+        """One ``ScenarioForecast`` of ``forecast``: the scenario solved on the baseline's ``z``, its own
+        summaries, and the summaries of the paired difference to the baseline's ``yhat``."""
+        step = t[1] - t[0]
+        lin = decoder_head.decoder_linear(self.dec)
+        with torch.no_grad():
+            res = None
+            if z.is_cuda and lin is not None:
+                res = ude_forecast.solve_decode_scenario(self.ode, z, t, step, lin, scenario, dynamics=dynamics)
+            if res is not None:
+                yhat_s, dyn, names, rates = res
+            else:
+                # the module's own layers (a CPU model, an ineligible decoder, outputs between grid points)
+                from ude_amd.schedule import build_schedule
+                sched = build_schedule(t, step)
+                table = scenario.table(ude_forecast.step_intervals(sched, t), self.n_regions, T=len(t))
+                latent, rates = ude_forecast._scenario_latent(self.ode, z, t, step, table)
+                yhat_s = self.dec(latent[..., :3]).reshape(len(t), n_samples * B, self.n_regions)
+                if dynamics:
+                    rows = ude_forecast._output_rows(scenario, len(t), self.n_regions)
+                    dyn, names = ude_forecast.latent_dynamics(self.ode, latent, rate_scale=rows)
+            out = ude_forecast.ensemble_summary(yhat_s, n_samples, B, scale=scaler, quantiles=quantiles)
+            if dynamics:
+                out.dynamics = ude_forecast.dynamics_summary(dyn, names, n_samples, B, quantiles=quantiles)
+            diff = yhat_s - yhat.detach()
+            effect = ude_forecast.ensemble_summary(diff, n_samples, B, scale=scaler, quantiles=quantiles)
+            effect_season = None
+            if season is not None:
+                out.season = ude_forecast.ensemble_season(yhat_s, n_samples, B, season, scale=scaler,
+                                                          quantiles=quantiles)
+                st = ude_forecast.ensemble_season(diff, n_samples, B, season.without_baseline(), scale=scaler,
+                                                  quantiles=quantiles)
+                effect_season = ude_forecast.SeasonEffect(st.total_mean, st.total_std, st.total_quantiles)
+        return ude_forecast.ScenarioForecast(out, effect, effect_season, rates)
 
     def _fused_head(self, y_pred, y_true, losses):
         """(nll, reg, per-group prediction mean / std) for this model's latest training prediction:

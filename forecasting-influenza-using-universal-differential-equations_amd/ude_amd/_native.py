@@ -157,6 +157,7 @@ _CABI: Dict[str, tuple] = {
     "ude_dopri_ratio": _sig(None, (3, _vp), (2, _f64), _vp, _pi64, _i32, _vp, _i32, _f64, (3, _vp)),
     "ude_rk4_forecast_dec": _sig("forecast_dec", _pd, _pp, (7, _vp), _pst, _vp),
     "ude_rk4_forecast_dyn": _sig("forecast_dyn", _pd, _pp, (8, _vp), _pst, _vp),
+    "ude_rk4_forecast_scn": _sig("forecast_scn", _pd, _pp, (9, _vp), _pst, _vp),
     "ude_forecast_summary_workspace": _sig(None, (5, _i32), _pi64),
     "ude_forecast_summary": _sig("forecast_summary", (4, _i32), (4, _vp), _i32, (6, _vp)),
     "ude_forecast_verify_workspace": _sig(None, (7, _i32), _pi64),

@@ -29,12 +29,18 @@ times between grid points).
 (ude_forecast_season): per sample the peak over the considered output times, when it falls, the total
 and the onset against a baseline -- the FluSight seasonal targets -- as a ``SeasonTargets`` of their
 distributions over the ensemble, scored against the observed season when targets are given.
+
+``Scenario`` is a counterfactual of the same forecast: multipliers of the rate net's beta and gamma per
+output interval and region.  ``solve_decode_scenario`` is the solve under it (ude_rk4_forecast_scn: every
+stage of an RK4 step scales the rates by the step's row before the flux), ``scenario_latent`` the same on
+the module's layers, and ``VAE.forecast(scenarios=...)`` returns per scenario a ``ScenarioForecast``: its
+own summaries and those of the paired difference to the baseline, solved on the same draw.
 """
 from __future__ import annotations
 
 import math
 from dataclasses import dataclass, fields
-from typing import Optional, Sequence, Tuple
+from typing import Dict, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -94,6 +100,10 @@ class Season:
                 raise ValueError("Season: baseline is a finite number or one per region")
             object.__setattr__(self, "baseline", float(base) if base.ndim == 0 else tuple(base.tolist()))
 
+    def without_baseline(self) -> "Season":
+        """The same considered times without an onset: for values that are not incidences (a difference)."""
+        return Season(None, self.start, self.every, self.run, self.window)
+
     def times(self, T: int) -> int:
         """M, the number of considered output indices of a T-point forecast."""
         if not self.start < T:
@@ -116,23 +126,27 @@ SEASON_SCORES = ("peak_time_skill", "onset_skill", "peak_value_skill", "peak_crp
 
 class _Result:
     """What the result containers (dataclasses) share.  A field holds a tensor, None, another container
-    (``Forecast.dynamics`` / ``.season``: handled by recursion) or something else that is carried through
-    (``Dynamics.names``)."""
+    (``Forecast.dynamics`` / ``.season``: handled by recursion), a dict of containers by name
+    (``Forecast.scenarios``: each in its place, in the dict's order) or something else that is carried
+    through (``Dynamics.names``)."""
 
     def _tensors(self):
         """``[(field name, tensor)]`` in field order, a nested container's in its place."""
         out = []
         for f in fields(self):
             v = getattr(self, f.name)
-            if isinstance(v, _Result):
-                out += v._tensors()
-            elif isinstance(v, torch.Tensor):
-                out.append((f.name, v))
+            for u in (v.values() if isinstance(v, dict) else (v,)):
+                if isinstance(u, _Result):
+                    out += u._tensors()
+                elif isinstance(u, torch.Tensor):
+                    out.append((f.name, u))
         return out
 
     def _map(self, fn):
         """The same container with ``fn`` applied to every tensor, in the order of ``_tensors``."""
         def go(v):
+            if isinstance(v, dict):
+                return {k: go(u) for k, u in v.items()}
             return v._map(fn) if isinstance(v, _Result) else fn(v) if isinstance(v, torch.Tensor) else v
         return type(self)(**{f.name: go(getattr(self, f.name)) for f in fields(self)})
 
@@ -147,11 +161,12 @@ class _Result:
 
     def numpy(self):
         """dict of numpy arrays by field name (absent fields None; a nested container: its ``numpy()`` dict;
-        ``Dynamics.names`` as it is)."""
+        a dict of containers: the dict of theirs; ``Dynamics.names`` as it is)."""
         host, out = self.cpu(), {}
+        conv = lambda v: v.numpy() if isinstance(v, (_Result, torch.Tensor)) else v
         for f in fields(host):
             v = getattr(host, f.name)
-            out[f.name] = v.numpy() if isinstance(v, (_Result, torch.Tensor)) else v
+            out[f.name] = {k: conv(u) for k, u in v.items()} if isinstance(v, dict) else conv(v)
         return out
 
 
@@ -238,7 +253,8 @@ class Forecast(_Result):
 
     ``dynamics``: the ``Dynamics`` of the same ensemble when it was asked for
     (``VAE.forecast(dynamics=True)``), else None.  ``season``: its ``SeasonTargets``
-    (``VAE.forecast(season=Season(...))``), else None."""
+    (``VAE.forecast(season=Season(...))``), else None.  ``scenarios``: name -> ``ScenarioForecast`` of
+    every scenario solved beside it on the same draw (``VAE.forecast(scenarios={...})``), else None."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
@@ -259,6 +275,150 @@ class Forecast(_Result):
     coverage_r: Optional[torch.Tensor] = None
     dynamics: Optional[Dynamics] = None
     season: Optional[SeasonTargets] = None
+    scenarios: Optional[Dict[str, "ScenarioForecast"]] = None
+
+
+@dataclass
+class RateStats(_Result):
+    """The side statistics of one solve (fp32, as the kernel's last workgroup writes them): ``mean`` / ``std``
+    (2,) of every beta and gamma that entered the flux (unbiased std) and ``fa_norm`` (1,), the norm of every
+    raw Fa -- what a fused solve records on the RHS for ``posterior()`` and the tracker.  Under a scenario
+    they are the scaled rates' and are returned with the scenario's result instead."""
+    mean: torch.Tensor
+    std: torch.Tensor
+    fa_norm: Optional[torch.Tensor] = None
+
+
+@dataclass
+class SeasonEffect(_Result):
+    """A scenario's effect on each trajectory's season total: the ``total_*`` fields of ``ensemble_season`` of
+    the paired difference (scenario - baseline).  The total is linear in the prediction, so this is the
+    distribution over the ensemble of the burden added (negative: averted), sample by sample."""
+    total_mean: torch.Tensor
+    total_std: torch.Tensor
+    total_quantiles: Optional[torch.Tensor] = None
+
+
+@dataclass
+class ScenarioForecast(_Result):
+    """One scenario of ``VAE.forecast(scenarios=...)``, solved on the baseline's draw.  ``forecast``: the
+    ``Forecast`` of the scenario's prediction (mean / std / quantiles; no scores: the observation did not
+    happen under the scenario; ``.dynamics`` / ``.season`` when they were asked for, the season without
+    targets).  ``effect``: the ``ensemble_summary`` of the paired difference ``y_hat_scenario - y_hat_baseline``
+    (same scale and quantiles).  ``effect_season``: its ``SeasonEffect`` when ``season`` was given.
+    ``rates``: the ``RateStats`` of the scenario's solve."""
+    forecast: Forecast
+    effect: Forecast
+    effect_season: Optional[SeasonEffect] = None
+    rates: Optional[RateStats] = None
+
+
+def _as_array(name: str, v) -> np.ndarray:
+    if isinstance(v, torch.Tensor):
+        v = v.detach().cpu().numpy()
+    try:
+        a = np.array(v.values if hasattr(v, "values") else v, dtype=np.float64)
+    except (TypeError, ValueError) as e:
+        raise ValueError(f"Scenario: {name} is not numeric") from e
+    if a.ndim > 2 or a.size < 1:
+        raise ValueError(f"Scenario: {name} is a scalar, a (T-1,) vector, a (R,) row or a (T-1, R) array, "
+                         f"not {a.shape}")
+    if not np.isfinite(a).all() or (a < 0).any():
+        raise ValueError(f"Scenario: every {name} multiplier must be finite and >= 0")
+    a.setflags(write=False)
+    return a
+
+
+@dataclass(frozen=True, eq=False)
+class Scenario:
+    """A counterfactual of the forecast: multipliers of the rate net's ``beta`` (transmission) and ``gamma``
+    (recovery) per output interval ``[t_j, t_{j+1})``, j = 0 .. T-2, and region.  Each of ``beta`` / ``gamma``
+    is a scalar, a ``(T-1,)`` vector (all regions), a ``(T-1, R)`` array, or a row that broadcasts over the
+    intervals -- ``(R,)`` (a 1-D argument of length T-1 is read per interval) or ``(1, R)``; every value
+    finite and >= 0.  ``table`` expands the intervals to the RK4 steps of a solve: all four stages of a step
+    use its interval's row, beta' = m_beta * |q0|, gamma' = m_gamma * |q1|; Fa is not scaled."""
+    beta: object = 1.0
+    gamma: object = 1.0
+
+    def __post_init__(self):
+        object.__setattr__(self, "beta", _as_array("beta", self.beta))
+        object.__setattr__(self, "gamma", _as_array("gamma", self.gamma))
+
+    @classmethod
+    def from_day(cls, T: int, start: int, beta=1.0, gamma=1.0) -> "Scenario":
+        """Ones before output interval ``start`` (0 <= start <= T-1) and ``beta`` / ``gamma`` (each a scalar
+        or one value per region) from it on, for a forecast of T output times."""
+        if isinstance(T, bool) or int(T) != T or int(T) < 2:
+            raise ValueError(f"Scenario.from_day: T {T!r} (at least 2 output times)")
+        if isinstance(start, bool) or int(start) != start or not 0 <= int(start) <= int(T) - 1:
+            raise ValueError(f"Scenario.from_day: start {start!r} (0 to {int(T) - 1})")
+
+        def ramp(name, v):
+            v = _as_array(name, v)
+            if v.ndim > 1:
+                raise ValueError(f"Scenario.from_day: {name} is a scalar or one value per region")
+            a = np.ones((int(T) - 1,) + v.shape)
+            a[int(start):] = v
+            return a
+        return cls(ramp("beta", beta), ramp("gamma", gamma))
+
+    def intervals(self, T: int, R: int) -> np.ndarray:
+        """The multipliers per output interval and region, ``(T-1, R, 2)`` fp32 ([..., 0]: beta)."""
+        n = int(T) - 1
+        out = np.empty((n, int(R), 2), dtype=np.float32)
+        for c, (name, a) in enumerate((("beta", self.beta), ("gamma", self.gamma))):
+            if a.ndim == 1 and a.shape[0] == n:
+                a = a[:, None]
+            if a.ndim == 1 and a.shape[0] not in (1, R) or a.ndim == 2 and (a.shape[0] not in (1, n)
+                                                                          or a.shape[1] not in (1, R)):
+                raise ValueError(f"Scenario: {name} {a.shape} does not fit {n} intervals x {R} regions")
+            out[..., c] = np.broadcast_to(a, (n, int(R)))
+        return out
+
+    def table(self, plan, R: int, T: Optional[int] = None) -> torch.Tensor:
+        """The ``(n_steps, R, 2)`` fp32 table (host) of a solve: ``plan`` is its launch plan or its
+        ``schedule.Schedule``.  Every output must be a grid hit, so that every step lies in one interval
+        (``step_intervals`` gives ``plan`` for an eager solve where they are not; ``T``: its output times)."""
+        steps = getattr(plan, "step_interval", None)
+        if steps is None:
+            out_k = _grid_hits(plan)
+            steps = np.repeat(np.arange(len(out_k) - 1), np.diff(np.asarray(out_k)))
+            n_int = len(out_k) - 1
+        else:
+            n_int = int(steps.max()) + 1 if T is None else int(T) - 1
+        rows = self.intervals(n_int + 1, R)
+        return torch.from_numpy(np.ascontiguousarray(rows[steps]))
+
+
+@dataclass
+class _Intervals:
+    step_interval: np.ndarray
+
+
+def step_intervals(schedule, t: torch.Tensor) -> _Intervals:
+    """What ``Scenario.table`` needs of a solve stepped by ``odeint(..., options=dict(step_size=...))`` on the
+    module's layers, whose outputs need not be grid hits: the output interval of every step, the last j with
+    ``t[j] <= grid[n]`` up to GRID_SNAP_ULPS roundings of the largest time.  On the forecast's daily grid
+    ``arange(T) / 7`` stepped by ``t[1] - t[0]`` the grid ``k * fl(1/7)`` misses ``fl(k / 7)`` by a rounding
+    (``_forecast_plan``): step k is then output interval k.  Where every output is a grid hit this is the
+    schedule's own expansion."""
+    th = t.detach().cpu().to(torch.float64)
+    tol = GRID_SNAP_ULPS * torch.finfo(t.dtype).eps * float(th.abs().max())
+    starts = schedule.grid[:-1].to(torch.float64) + tol
+    j = torch.searchsorted(th, starts, right=True) - 1
+    return _Intervals(j.clamp(0, len(th) - 2).numpy())
+
+
+def _grid_hits(plan) -> Sequence[int]:
+    """The grid point of every output time of a launch plan or schedule whose outputs are all grid hits."""
+    out_k = getattr(plan, "out_k", None)
+    if out_k is None and hasattr(plan, "out_start"):
+        if plan.n_steps >= 1 and all(int(m) == 1 for m in plan.out_mode):
+            out_k = [0] + [n + 1 for n in range(plan.n_steps)
+                           for _ in range(int(plan.out_start[n + 1] - plan.out_start[n]))]
+    if out_k is None:
+        raise ValueError("Scenario: an output time of this solve is not a grid point (intervals do not map to steps)")
+    return out_k
 
 
 def _scale_vector(scale, R: int, device) -> Optional[torch.Tensor]:
@@ -604,12 +764,25 @@ def _forecast_plan(ode, y0, t, step_size):
     return plan
 
 
+def _scenario_table(scenario, plan, R: int, dev) -> torch.Tensor:
+    """The device table of ``scenario`` -- a ``Scenario``, or an fp32 ``(n_steps, R, 2)`` tensor that is read in
+    place when it is contiguous and 8-byte aligned on ``dev``."""
+    shape = (int(plan.prob.n_steps), int(R), 2)
+    if isinstance(scenario, Scenario):
+        return scenario.table(plan, R).to(dev)
+    if not isinstance(scenario, torch.Tensor) or tuple(scenario.shape) != shape:
+        raise ValueError(f"solve_decode_scenario: scenario is a Scenario or a {shape} table")
+    table = scenario.detach().to(device=dev, dtype=torch.float32).contiguous()
+    return table.clone() if table.data_ptr() % 8 else table
+
+
 def _solve_decode(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear, n_dyn: int = 0,
-                  out: Optional[torch.Tensor] = None) -> Optional[Tuple[torch.Tensor, Optional[torch.Tensor]]]:
+                  out: Optional[torch.Tensor] = None, scenario=None):
     """The inference solve with the decoder epilogue behind ``solve_decode_forecast`` (``n_dyn`` = 0:
-    ude_rk4_forecast_dec) and ``solve_decode_dynamics`` (``n_dyn`` channels into ``out`` or a new tensor:
-    ude_rk4_forecast_dyn): ``(y_hat, dyn or None)``, or None when an output time is not a grid point.
-    Records the solve's side statistics on ``ode``."""
+    ude_rk4_forecast_dec), ``solve_decode_dynamics`` (``n_dyn`` channels into ``out`` or a new tensor:
+    ude_rk4_forecast_dyn) and ``solve_decode_scenario`` (``scenario``: ude_rk4_forecast_scn): ``(y_hat, dyn or
+    None, RateStats)``, or None when an output time is not a grid point.  Without a scenario the solve's
+    side statistics are recorded on ``ode``; a scenario's belong to the counterfactual and are only returned."""
     with torch.no_grad(), torch.cuda.device(y0.device):
         plan = _forecast_plan(ode, y0, t, step_size)
         if plan.out_k is None:
@@ -646,6 +819,12 @@ def _solve_decode(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear, n_d
         head = (plan.desc, plan.prob, pack.data_ptr(), plan.sched_dev.data_ptr(), y0.data_ptr(), dec_pack.data_ptr(),
                 yhat.data_ptr())
         tail = (stats_slab.data_ptr(), _fused._ctl(plan, dev).data_ptr(), st, stream)
+        rates = RateStats(*stats)
+        if scenario is not None:
+            table = _scenario_table(scenario, plan, R, dev)
+            with _fused._timed("forecast_scn"):
+                plan.lib.forecast_scn(*head[:-1], table.data_ptr(), yhat.data_ptr(), _fused._ptr(dyn), *tail)
+            return yhat, dyn, rates
         if dyn is None:
             with _fused._timed("forecast_dec"):
                 plan.lib.forecast_dec(*head, *tail)
@@ -653,7 +832,7 @@ def _solve_decode(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear, n_d
             with _fused._timed("forecast_dyn"):
                 plan.lib.forecast_dyn(*head, dyn.data_ptr(), *tail)
         ode._record_fused(stats, plan.n_eval, sums=sums)
-    return yhat, dyn
+    return yhat, dyn, rates
 
 
 def solve_decode_forecast(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear) -> Optional[torch.Tensor]:
@@ -682,7 +861,76 @@ def solve_decode_dynamics(ode, y0: torch.Tensor, t: torch.Tensor, step_size, lin
         return None
     names = dynamics_names(ode)
     res = _solve_decode(ode, y0, t, step_size, linear, len(names), out)
-    return None if res is None else (*res, names)
+    return None if res is None else (res[0], res[1], names)
+
+
+def solve_decode_scenario(ode, y0: torch.Tensor, t: torch.Tensor, step_size, linear, scenario, dynamics: bool = False,
+                          out: Optional[torch.Tensor] = None):
+    """``solve_decode_forecast`` under a scenario (ude_rk4_forecast_scn): ``(y_hat (T, N, R), dyn (C, T, N, R)
+    or None, names, RateStats)``.  ``scenario``: a ``Scenario``, or its ``(n_steps, R, 2)`` fp32 table.  All
+    four stages of RK4 step k scale the rate net's outputs of region r by row k before the flux (beta' =
+    m_beta |q0|, gamma' = m_gamma |q1|; Fa, the mask and the update unchanged), so a scenario of ones gives
+    ``solve_decode_forecast``'s bits.  With ``dynamics`` the channels of ``solve_decode_dynamics`` (into
+    ``out`` when given) report what entered the flux: beta', gamma', r_eff = beta' s / gamma'; an output that
+    starts a step uses that step's row, the last output the last step's.  The ``RateStats`` are the scaled
+    rates'; nothing is recorded on ``ode``.  None where ``solve_decode_dynamics`` gives None and for a model
+    without a rate net (Fa)."""
+    if getattr(ode, "uncertainty", "none") == "bayes" or ode.ode_type not in ("Fp", "FaFp") \
+            or not decoder_head.eligible(ode, y0, linear):
+        return None
+    names = dynamics_names(ode)
+    res = _solve_decode(ode, y0, t, step_size, linear, len(names) if dynamics else 0, out, scenario)
+    return None if res is None else (res[0], res[1], names, res[2])
+
+
+def _output_rows(scenario: Scenario, T: int, R: int) -> torch.Tensor:
+    """The multipliers behind every output's dynamics, ``(T, R, 2)``: those of the step that starts at the
+    output -- its interval's --, the last interval's for the last output."""
+    rows = scenario.intervals(T, R)
+    return torch.from_numpy(rows[list(range(T - 1)) + [T - 2]])
+
+
+def _scenario_latent(ode, y0: torch.Tensor, t: torch.Tensor, step_size, table: torch.Tensor):
+    """``scenario_latent`` and the ``RateStats`` of its evaluations (in the latent's dtype)."""
+    from .solvers import _step_rk4
+    from .schedule import fixed_grid
+    grid = fixed_grid(t, step_size).to(y0.device)
+    if tuple(table.shape) != (len(grid) - 1, ode.n_regions, 2):
+        raise ValueError(f"scenario_latent: table {tuple(table.shape)} is not ({len(grid) - 1}, {ode.n_regions}, 2)")
+    table = table.detach().to(device=y0.device, dtype=y0.dtype)
+    tt = t.to(y0.device)
+    kept = (ode._params, ode.tracker)
+    ode._params, ode.tracker = [], []                 # the attribute, not the property: no reset of fused statistics
+    try:
+        with torch.no_grad():
+            out, j, y = [y0], 1, y0
+            for n in range(len(grid) - 1):
+                ode.rate_scale = table[n]
+                t0, t1 = grid[n], grid[n + 1]
+                y1 = y + _step_rk4(ode, t0, t1 - t0, t1, y)
+                while j < len(tt) and t1 >= tt[j]:
+                    out.append(y if tt[j] == t0 else y1 if tt[j] == t1 else y + (tt[j] - t0) / (t1 - t0) * (y1 - y))
+                    j += 1
+                y = y1
+            latent = torch.stack(out, 0)
+            p = torch.stack(ode._params).reshape(-1, 2)
+            fa = torch.norm(torch.stack(ode.tracker)).reshape(1) if ode.tracker else None
+            return latent, RateStats(p.mean(0), p.std(0), fa)
+    finally:
+        ode.rate_scale = None
+        ode._params, ode.tracker = kept
+
+
+def scenario_latent(ode, y0: torch.Tensor, t: torch.Tensor, step_size, table: torch.Tensor) -> torch.Tensor:
+    """The latent ``(T, N, R, L)`` of the solve under a scenario on the module's own layers: the fixed-grid
+    3/8-rule loop of ``odeint(method='rk4')`` (``solvers.eager_fixed_grid``, the same operations in the same
+    order) with ``ode.rate_scale = table[k]`` during step k -- all four stages, the one at the step's end
+    time included -- under ``no_grad``.  ``table``: ``(n_steps, R, 2)`` for the grid of ``t`` / ``step_size``.
+    Leaves ``ode.params`` / ``ode.tracker`` as they were and ``rate_scale`` None, also after an exception.
+    Serves a CPU model, an ineligible decoder and every case ``solve_decode_scenario`` gives None for."""
+    if ode.ode_type not in ("Fp", "FaFp"):
+        raise ValueError("scenario_latent: a scenario scales the rate net's beta and gamma; this model has none")
+    return _scenario_latent(ode, y0, t, step_size, table)[0]
 
 
 def _mean_stack(stack, h: torch.Tensor) -> torch.Tensor:
@@ -697,13 +945,16 @@ def _mean_stack(stack, h: torch.Tensor) -> torch.Tensor:
     return h
 
 
-def latent_dynamics(ode, latent: torch.Tensor) -> Tuple[torch.Tensor, Tuple[str, ...]]:
+def latent_dynamics(ode, latent: torch.Tensor, rate_scale: Optional[torch.Tensor] = None
+                    ) -> Tuple[torch.Tensor, Tuple[str, ...]]:
     """The channels of ``solve_decode_dynamics`` from a written latent (T, N, R, L), in its dtype:
     ``(dyn (C, T, N, R), names)``.  The state is ``latent[..., :3]``; the nets are evaluated once at every
     output state without touching ``ode.params`` / ``ode.tracker`` (on a HIP device by the evaluation
     kernel, ude_amd/eval_rhs.py, else by the module's layers); ``r_eff = beta * s / gamma`` in the latent's
     dtype.  A Bayesian RHS is evaluated at its MEAN weights (no draw is taken from its stream): the
-    rates and flux of the posterior mean network, not of the per-evaluation samples of the solve."""
+    rates and flux of the posterior mean network, not of the per-evaluation samples of the solve.
+    ``rate_scale`` (T, R, 2): a scenario's multipliers per output time -- beta and gamma are scaled by them
+    (one rounding each) before ``r_eff``, as ``solve_decode_scenario`` reports them."""
     names = dynamics_names(ode)
     with torch.no_grad():
         lat = latent.detach()
@@ -723,6 +974,8 @@ def latent_dynamics(ode, latent: torch.Tensor) -> Tuple[torch.Tensor, Tuple[str,
             if "fa_s" in names:
                 fa = _mean_stack(ode.aug_net if bayes else ode._a_stack(), h).reshape(T * N, R, 3)
         ch = [x[..., 0], x[..., 1], x[..., 2]]
+        if rate_scale is not None and rates is not None:
+            rates = (rates.reshape(T, N, R, 2) * rate_scale.to(rates).reshape(T, 1, R, 2)).reshape(T * N, R, 2)
         if "beta" in names:
             ch += [rates[..., 0], rates[..., 1], rates[..., 0] * x[..., 0] / rates[..., 1]]
         if "fa_s" in names:

@@ -150,6 +150,10 @@ class _UDEModule(nn.Module):
     # one (N, R, 3) A-net tensor per RHS evaluation, as the reference's forward appends them
     # (lib/models.py:137, :187, :238, :252); recomputed from the solve's stage checkpoints
     materialize_tracking = False
+    # a scenario's multipliers (R, 2) of (beta, gamma) for the evaluations made while it is set
+    # (ude_amd.forecast.scenario_latent sets it step by step): the eager forward scales the rates after
+    # ``abs``, before they are appended and enter the flux; None: the model as it is
+    rate_scale = None
 
     def _init_tracking(self):
         self.params = []
@@ -276,6 +280,10 @@ class _UDEModule(nn.Module):
             out += [lin.weight.shape, lin.bias.shape]
         return out
 
+    def _scaled(self, rates: torch.Tensor) -> torch.Tensor:
+        """The rates (N, R, 2) under ``rate_scale`` (one rounding per rate: fl(m * |q|))."""
+        return rates if self.rate_scale is None else rates * self.rate_scale.to(rates)
+
     def _eval_weights(self) -> List[torch.Tensor]:
         out: List[torch.Tensor] = []
         for lin in self.ude_linears():
@@ -285,8 +293,8 @@ class _UDEModule(nn.Module):
     def _fused_forward(self, x: torch.Tensor):
         """forward() on the gfx950 evaluation kernel when x lives on a HIP device (else None):
         the same return value and the same params / tracker entries as the eager code."""
-        if not (x.is_cuda and self.fused_eval):
-            return None
+        if self.rate_scale is not None or not (x.is_cuda and self.fused_eval):
+            return None                       # the evaluation kernel knows nothing of a rate_scale
         from . import eval_rhs
         if not eval_rhs.eligible(self, x):
             return None
@@ -318,7 +326,7 @@ class Fp(_UDEModule):
         f = self._fused_forward(x)
         if f is not None:
             return f
-        rates = torch.abs(_run_stack(self.Fp_net, x)).reshape(-1, self.n_regions, 2)
+        rates = self._scaled(torch.abs(_run_stack(self.Fp_net, x)).reshape(-1, self.n_regions, 2))
         self.params.append(rates)
         return _finish(_sir_flux(rates, x), x)
 
@@ -377,7 +385,7 @@ class FaFp(_UDEModule):
         f = self._fused_forward(x)
         if f is not None:
             return f
-        rates = torch.abs(_run_stack(self.net, x)).reshape(-1, self.n_regions, 2)
+        rates = self._scaled(torch.abs(_run_stack(self.net, x)).reshape(-1, self.n_regions, 2))
         self.params.append(rates)
         fa = _run_stack(self.aug_net, x).reshape(-1, self.n_regions, 3)
         res = _finish(_sir_flux(rates, x) + self.Fa_w * fa, x)

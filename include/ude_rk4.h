@@ -390,6 +390,27 @@ int ude_rk4_forecast_dyn(const UdeModelDesc* m, const UdeProblem* p, const float
                          const float* y0, const float* dec_pack, float* yhat, float* dyn, double* stats_slab,
                          uint32_t* ctl, const UdeSideStats* stats, ude_stream_t stream);
 
+/* ude_rk4_forecast_scn: ude_rk4_forecast_dec under a scenario -- "transmission falls 30 % in these regions
+ * from day 10".  scn is a table (n_steps, R, 2) of fp32 multipliers, 8-byte aligned, every entry finite and
+ * >= 0: scn[k][r][0] scales beta and scn[k][r][1] scales gamma of region r in RK4 step k.
+ *   per step, not per time   all four stage evaluations of step k use row k -- also the stage at the
+ *                            step's end time, which the next step's first stage shares: a right-hand
+ *                            side that jumps at a grid point is integrated piece by piece
+ *   what is scaled           beta' = fl(m_beta |q0|), gamma' = fl(m_gamma |q1|) in fp32 (q: the rate net's
+ *                            outputs); then plus = (beta' S) I, minus = gamma' I, + Fa_w Fa and the mask as
+ *                            ever.  Fa is not scaled.  A table of ones gives ude_rk4_forecast_dec's bits
+ *   dyn (nullable)           the channels of ude_rk4_forecast_dyn with beta = beta', gamma = gamma',
+ *                            r_eff = (beta' s) / gamma' (one fp32 division of the emitted channels); an
+ *                            output that starts a step uses that step's row, the last output the last
+ *                            step's row (n_steps - 1)
+ *   stats                    the side statistics of the scaled rates (they belong to the scenario)
+ * Other arguments and preconditions as ude_rk4_forecast_dyn.  Kinds with a rate net only (UDE_E_UNSUPPORTED
+ * for Fa, for UDE_KIND_BAYES and with UdeProblem.recompute); UDE_E_INVALID for a null or misaligned scn or
+ * n_steps < 1.  A host expands per-output-interval multipliers to steps with the schedule's out_start. */
+int ude_rk4_forecast_scn(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,
+                         const float* y0, const float* dec_pack, const float* scn, float* yhat, float* dyn,
+                         double* stats_slab, uint32_t* ctl, const UdeSideStats* stats, ude_stream_t stream);
+
 /* Ensemble summary of y_hat (T, S*B, R) (sample n = s*B + b; no model): for every group (t, b, r) the S
  * values v_s = (double)y_hat[t, s*B+b, r] * scale[r] give mean, population std (ddof 0, two passes) and
  * quant[k] = numpy.quantile(v, q[k]) ('linear'; S <= 1024 when n_q > 0, NaN inputs undefined); with

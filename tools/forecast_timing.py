@@ -31,11 +31,19 @@ region, targets given) of one y_hat (57, 8192, 49) resident on the device, two r
   (b) device: ude_amd.forecast.ensemble_season(...).cpu() -- ude_forecast_season and one stacked copy of
       its results.
 
+``--scenario`` times the solve kernel under a scenario (ude_rk4_forecast_scn) against the solves without one,
+on one draw z (8192, 49, 8) resident on the device, five calls taking turns: ``forecast_dec``; ``forecast_scn``
+with a table of ones; ``forecast_scn`` with a table in which every (step, region) differs; ``forecast_dyn``;
+``forecast_scn`` with the dynamics channels.  The figure to read is each call's own event time
+(``native_calls_ms``).  On a tree without scenarios only the two solves it has are timed (the yardstick of
+the commit before).
+
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
 (ude_amd.fused.EVENTS).  Prints one JSON line.
 
-    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128] [--dynamics | --season]
+    python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128]
+                                    [--dynamics | --season | --scenario]
 """
 import argparse
 import importlib
@@ -102,6 +110,7 @@ def main():
     ap.add_argument("--samples", type=int, default=128)
     ap.add_argument("--dynamics", action="store_true", help="time the dynamics paths instead (see the docstring)")
     ap.add_argument("--season", action="store_true", help="time the seasonal targets instead (see the docstring)")
+    ap.add_argument("--scenario", action="store_true", help="time the scenario solve instead (see the docstring)")
     a = ap.parse_args()
     R, B, S, window = 49, a.batch, a.samples, 8
     torch.manual_seed(0)
@@ -206,6 +215,53 @@ def main():
                           "scores_rel_diff_device_vs_host": agree, "histograms_equal": same_hist,
                           "host_route": res_a, "device_route": res_b,
                           "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}))
+        return
+
+    if a.scenario:
+        from ude_amd import decoder_head
+        from ude_amd import forecast as fcast
+        T = len(t)
+        lin = decoder_head.decoder_linear(model.dec)
+        with torch.no_grad():
+            mean, std = model.enc(x)
+            eps = torch.randn(S, B, R, model.ld_enc, device="cuda")
+            z = (models.reparam(eps, std, mean, S, B, uncertainty=True) + 1e-5).contiguous()
+        step = t[1] - t[0]
+        C = len(fcast.dynamics_names(model.ode))
+        dyn_out = torch.empty((C, T, S * B, R), dtype=torch.float32, device="cuda")
+
+        def solve(fn, *extra, **kw):
+            def run(e1=None):
+                res = fn(model.ode, z, t, step, lin, *extra, **kw)
+                assert res is not None
+                model.ode.clear_tracking()
+                if e1 is not None:
+                    e1.record()
+                return res
+            return run
+
+        routes = {"forecast_dec": solve(fcast.solve_decode_forecast),
+                  "forecast_dyn": solve(fcast.solve_decode_dynamics, out=dyn_out)}
+        checks = {}
+        if hasattr(fcast, "solve_decode_scenario"):
+            n_steps = fcast._forecast_plan(model.ode, z, t, step).prob.n_steps
+            k, r = torch.arange(n_steps).view(-1, 1), torch.arange(R).view(1, -1)
+            ones = torch.ones(n_steps, R, 2, device="cuda")
+            mixed = torch.stack([0.5 + 0.1 * ((3 * k + r) % 7).float(), 0.8 + 0.05 * ((k + 2 * r) % 5).float()], -1).cuda()
+            routes = {"forecast_dec": routes["forecast_dec"],
+                      "forecast_scn_ones": solve(fcast.solve_decode_scenario, ones),
+                      "forecast_scn_table": solve(fcast.solve_decode_scenario, mixed),
+                      "forecast_dyn": routes["forecast_dyn"],
+                      "forecast_scn_dyn": solve(fcast.solve_decode_scenario, mixed, dynamics=True, out=dyn_out)}
+            checks["ones_equal_forecast_dec"] = bool(torch.equal(routes["forecast_scn_ones"]()[0],
+                                                                 routes["forecast_dec"]()))
+            checks["table_changes_the_forecast"] = not bool(torch.equal(routes["forecast_scn_table"]()[0],
+                                                                        routes["forecast_dec"]()))
+        res = timed_alternating(list(routes.values()), a.runs, a.warmup)
+        print(json.dumps({"tool": "forecast_timing --scenario", "commit": commit_of(),
+                          "device": torch.cuda.get_device_name(0),
+                          "shape": {"R": R, "L": 8, "S": S, "B": B, "N": S * B, "T": T, "C": C},
+                          **checks, **dict(zip(routes, res))}))
         return
 
     if a.dynamics:
