@@ -7,6 +7,7 @@
 #include "ude_vec.h"      // model-independent vector kernels (compiled in both passes)
 #include "ude_forecast.h" // model-independent ensemble summary kernels (likewise)
 #include "ude_season.h"   // model-independent seasonal-target kernels (likewise)
+#include "ude_joint.h"    // model-independent energy / variogram score kernels (likewise)
 
 // This translation unit is host code only (no kernels are instantiated here).
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -349,6 +350,19 @@ int ude_forecast_season(int32_t T, int32_t S, int32_t B, int32_t R, int32_t star
                         double* peak_time, double* onset, double* overall, double* region, ude_stream_t stream) {
   return ude::forecast_season(T, S, B, R, start, every, run, window, yhat, scale, base, y_true, q, n_q, ws, stats,
                               quant, peak_time, onset, overall, region, (hipStream_t)stream);
+}
+
+int ude_forecast_joint_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every,
+                                 int32_t p_code, int64_t* ws_bytes) {
+  return ude::forecast_joint_workspace(T, S, B, R, start, every, p_code, ws_bytes);
+}
+
+int ude_forecast_joint(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every, int32_t p_code,
+                       const float* yhat, const double* scale, const float* y_true, void* ws, double* e_joint,
+                       double* e_series, double* e_field, double* v_series, double* v_field, double* means,
+                       ude_stream_t stream) {
+  return ude::forecast_joint(T, S, B, R, start, every, p_code, yhat, scale, y_true, ws, e_joint, e_series, e_field,
+                             v_series, v_field, means, (hipStream_t)stream);
 }
 
 #ifdef UDE_PROFILE

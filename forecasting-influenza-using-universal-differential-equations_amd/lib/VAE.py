@@ -211,7 +211,7 @@ class VAE:
         return y_pred
 
     def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False,
-                 season=None, scenarios=None):
+                 season=None, scenarios=None, joint=None):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
@@ -248,7 +248,20 @@ class VAE:
         ``ude_amd.forecast.scenario_latent``), so ``effect`` -- the summary of the paired difference
         scenario - baseline -- carries no sampling noise of its own.  A scenario's side statistics are
         returned in ``rates`` and never recorded on the RHS.  An RHS without a rate net (Fa) or a Bayesian
-        one raises ValueError."""
+        one raises ValueError.
+
+        ``joint`` -- True (``ude_amd.forecast.Joint()``) or a ``Joint`` -- also fills ``Forecast.joint``
+        (``ude_amd.forecast.JointScores``): the energy and variogram scores of each window's trajectories
+        against ``y_true`` (required), which see the dependence between days and between regions that no
+        per-day score does, from the same prediction on every route (ude_forecast_joint on the device).
+        Scenarios get none: the observation did not happen under them.  With ``joint=None`` nothing changes."""
+        if joint is True:
+            joint = ude_forecast.Joint()
+        if joint is not None:
+            if not isinstance(joint, ude_forecast.Joint):
+                raise TypeError("forecast: joint is None, True or an ude_amd.forecast.Joint")
+            if y_true is None:
+                raise ValueError("forecast: joint needs the targets y_true")
         if scenarios is not None:
             scenarios = dict(scenarios)
             for name, sc in scenarios.items():
@@ -307,6 +320,8 @@ class VAE:
         if season is not None:
             fc.season = ude_forecast.ensemble_season(yhat, n_samples, B, season, y_true=y_true, scale=scaler,
                                                      quantiles=quantiles)
+        if joint is not None:
+            fc.joint = ude_forecast.ensemble_joint(yhat, n_samples, B, y_true, joint, scale=scaler)
         if scenarios is not None:
             fc.scenarios = {name: self._forecast_scenario(sc, z, t, yhat, n_samples, B, scaler, quantiles, dynamics,
                                                           season) for name, sc in scenarios.items()}

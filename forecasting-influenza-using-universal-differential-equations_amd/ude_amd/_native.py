@@ -164,6 +164,8 @@ _CABI: Dict[str, tuple] = {
     "ude_forecast_verify": _sig("forecast_verify", (4, _i32), (4, _vp), _i32, _vp, (2, _i32), (8, _vp)),
     "ude_forecast_season_workspace": _sig(None, (9, _i32), _pi64),
     "ude_forecast_season": _sig("forecast_season", (8, _i32), (5, _vp), _i32, (8, _vp)),
+    "ude_forecast_joint_workspace": _sig(None, (7, _i32), _pi64),
+    "ude_forecast_joint": _sig("forecast_joint", (7, _i32), (11, _vp)),
     "ude_build_info": _sig(None),
 }
 EXPORTED_SYMBOLS = tuple(_CABI)
@@ -261,6 +263,9 @@ class NativeLib:
 
     def forecast_season_workspace(self, T, S, B, R, n_q, start, every, run, window) -> int:
         return self._workspace("ude_forecast_season_workspace", T, S, B, R, n_q, start, every, run, window)
+
+    def forecast_joint_workspace(self, T, S, B, R, start, every, p_code) -> int:
+        return self._workspace("ude_forecast_joint_workspace", T, S, B, R, start, every, p_code)
 
     def lincomb(self, n, base, ks: Sequence[int], coef, out, stream) -> None:
         arr = (ctypes.c_void_p * len(ks))(*ks)

@@ -35,6 +35,11 @@ output interval and region.  ``solve_decode_scenario`` is the solve under it (ud
 stage of an RK4 step scales the rates by the step's row before the flux), ``scenario_latent`` the same on
 the module's layers, and ``VAE.forecast(scenarios=...)`` returns per scenario a ``ScenarioForecast``: its
 own summaries and those of the paired difference to the baseline, solved on the same draw.
+
+``ensemble_joint`` scores the trajectories jointly (ude_forecast_joint): the energy score and the variogram
+score of a window's S trajectories against the observed one, on region r's series, on the field of the
+regions at one time and on all considered coordinates at once -- the scores that tell an ensemble whose days
+and regions move together from one with the same marginals that does not -- as a ``JointScores``.
 """
 from __future__ import annotations
 
@@ -123,10 +128,37 @@ class Season:
 
 SEASON_SCORES = ("peak_time_skill", "onset_skill", "peak_value_skill", "peak_crps", "total_crps")
 
+MAX_JOINT_COORDS = 4096                  # JS_MAX_C (csrc/ude_joint.h): regions and considered times on the device
+
+
+@dataclass(frozen=True)
+class Joint:
+    """What ``joint=`` considers: the output indices ``t_m = start + m * every`` as ``Season`` has them, and
+    the variogram's order ``p``, 0.5 or 1.0."""
+    start: int = 0
+    every: int = 1
+    p: float = 0.5
+
+    def __post_init__(self):
+        for name, low in (("start", 0), ("every", 1)):
+            v = getattr(self, name)
+            if isinstance(v, bool) or int(v) != v or int(v) < low or int(v) > 2 ** 31 - 1:
+                raise ValueError(f"Joint: {name} {v!r} (an integer >= {low})")
+            object.__setattr__(self, name, int(v))
+        if isinstance(self.p, bool) or self.p not in (0.5, 1.0):
+            raise ValueError(f"Joint: p {self.p!r} (0.5 or 1.0)")
+        object.__setattr__(self, "p", float(self.p))
+
+    def times(self, T: int) -> int:
+        """M, the number of considered output indices of a T-point forecast."""
+        if not self.start < T:
+            raise ValueError(f"Joint: start {self.start} is not below the {T} output times")
+        return -((self.start - T) // self.every)
+
 
 class _Result:
     """What the result containers (dataclasses) share.  A field holds a tensor, None, another container
-    (``Forecast.dynamics`` / ``.season``: handled by recursion), a dict of containers by name
+    (``Forecast.dynamics`` / ``.season`` / ``.joint``: handled by recursion), a dict of containers by name
     (``Forecast.scenarios``: each in its place, in the dict's order) or something else that is carried
     through (``Dynamics.names``)."""
 
@@ -206,6 +238,29 @@ class SeasonTargets(_Result):
     total_crps_r: Optional[torch.Tensor] = None
 
 
+@dataclass
+class JointScores(_Result):
+    """The joint scores of an ensemble forecast against the observed trajectory (fp64 tensors on the
+    forecast's device), over the M considered output indices of a ``Joint``: the energy score ``ES_C = mean_i
+    |x_i - y|_C - mean_ij |x_i - x_j|_C / 2`` (Euclidean norm over the block's coordinates) and the unweighted
+    variogram score of order p ``VS_C = sum_{c < c'} (|y_c - y_c'|^p - mean_s |x_sc - x_sc'|^p)^2`` of a window's
+    S trajectories, on the blocks series (b, r) -- region r's M times: ``energy_series`` / ``variogram_series``
+    (B, R) --, field (b, m) -- the R regions at time m: ``energy_field`` / ``variogram_field`` (B, M) -- and
+    joint (b) -- all M * R coordinates: ``energy_joint`` (B,).  ``energy_joint_mean`` (0-dim), ``*_r`` (R,) and
+    ``*_t`` (M,) are their means over the B windows.  In one dimension the energy score is the CRPS; a block of
+    one coordinate has variogram score 0."""
+    energy_joint: torch.Tensor
+    energy_series: torch.Tensor
+    energy_field: torch.Tensor
+    variogram_series: torch.Tensor
+    variogram_field: torch.Tensor
+    energy_joint_mean: torch.Tensor
+    energy_series_r: torch.Tensor
+    energy_field_t: torch.Tensor
+    variogram_series_r: torch.Tensor
+    variogram_field_t: torch.Tensor
+
+
 DYN_STATE = ("s", "i", "r")
 DYN_RATES = ("beta", "gamma", "r_eff")
 DYN_FLUX = ("fa_s", "fa_i", "fa_r")
@@ -254,7 +309,8 @@ class Forecast(_Result):
     ``dynamics``: the ``Dynamics`` of the same ensemble when it was asked for
     (``VAE.forecast(dynamics=True)``), else None.  ``season``: its ``SeasonTargets``
     (``VAE.forecast(season=Season(...))``), else None.  ``scenarios``: name -> ``ScenarioForecast`` of
-    every scenario solved beside it on the same draw (``VAE.forecast(scenarios={...})``), else None."""
+    every scenario solved beside it on the same draw (``VAE.forecast(scenarios={...})``), else None.
+    ``joint``: its ``JointScores`` (``VAE.forecast(joint=True)`` or a ``Joint``), else None."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
@@ -276,6 +332,7 @@ class Forecast(_Result):
     dynamics: Optional[Dynamics] = None
     season: Optional[SeasonTargets] = None
     scenarios: Optional[Dict[str, "ScenarioForecast"]] = None
+    joint: Optional[JointScores] = None
 
 
 @dataclass
@@ -736,6 +793,93 @@ def ensemble_season(values: torch.Tensor, n_samples: int, batch: int, season: Se
     if yt is not None:
         _set_season_scores(out, overall, region, base is not None)
     return out
+
+
+JOINT_CHUNK = 1 << 25                    # elements of the torch route's largest temporary (fp64: 256 MB)
+
+
+def _window_mean(x: torch.Tensor) -> torch.Tensor:
+    """The mean over dim 0 as the kernels' fc_group_mean forms it: x[0] + x[1] + .., divided once."""
+    acc = x[0].clone()
+    for b in range(1, x.shape[0]):
+        acc = acc + x[b]
+    return acc / x.shape[0]
+
+
+def _variogram_torch(x: torch.Tensor, y: torch.Tensor, p: float) -> torch.Tensor:
+    """The variogram score of every block: x (C, S, ...) the samples and y (C, ...) the target at the block's C
+    coordinates -> (...).  One coordinate at a time against those after it: the temporary is (C, S, ...)."""
+    power = (lambda d: d.abs().sqrt()) if p == 0.5 else (lambda d: d.abs())
+    out = torch.zeros(y.shape[1:], dtype=torch.float64, device=x.device)
+    for c in range(x.shape[0] - 1):
+        mean = power(x[c + 1:] - x[c]).sum(1) / x.shape[1]
+        out = out + ((power(y[c + 1:] - y[c]) - mean) ** 2).sum(0)
+    return out
+
+
+def _joint_torch(yhat, S, B, joint: Joint, M, y_true, scale) -> JointScores:
+    T, N, R = yhat.shape
+    v_all = yhat.detach()[joint.start::joint.every].to(torch.float64).reshape(M, S, B, R)
+    y_all = y_true.detach().to(device=yhat.device, dtype=torch.float64).permute(1, 0, 2)[joint.start::joint.every]
+    if scale is not None:
+        v_all, y_all = v_all * scale, y_all * scale                                    # (M, S, B, R), (M, B, R)
+    nb = max(1, min(B, JOINT_CHUNK // (M * S * R)))                                   # windows per chunk
+    cols = [[] for _ in range(5)]
+    for b0 in range(0, B, nb):
+        v, y = v_all[:, :, b0:b0 + nb], y_all[:, b0:b0 + nb]
+        n = v.shape[2]
+        d2 = (v - y.unsqueeze(1)) ** 2                                                 # the first term
+        first = [d2.sum((0, 3)).sqrt().sum(0), d2.sum(0).sqrt().sum(0), d2.sum(3).sqrt().sum(1)]
+        pairs = [torch.zeros_like(f) for f in first]                                   # (n,), (n, R), (M, n)
+        ni = max(1, min(S, JOINT_CHUNK // (M * S * n * R)))                            # samples i per chunk
+        for i0 in range(0, S, ni):
+            d2 = (v[:, i0:i0 + ni, None] - v[:, None]) ** 2                            # (M, ni, S, n, R)
+            pairs[0] = pairs[0] + d2.sum((0, 4)).sqrt().sum((0, 1))
+            pairs[1] = pairs[1] + d2.sum(0).sqrt().sum((0, 1))
+            pairs[2] = pairs[2] + d2.sum(4).sqrt().sum((1, 2))
+        es = [f / S - q / (2.0 * S * S) for f, q in zip(first, pairs)]
+        cols[0].append(es[0])
+        cols[1].append(es[1])
+        cols[2].append(es[2].t())
+        cols[3].append(_variogram_torch(v, y, joint.p))                                # blocks (n, R) over M
+        cols[4].append(_variogram_torch(v.permute(3, 1, 2, 0), y.permute(2, 1, 0), joint.p))  # blocks (n, M) over R
+    e_joint, e_series, e_field, v_series, v_field = (torch.cat(c).contiguous() for c in cols)
+    return JointScores(e_joint, e_series, e_field, v_series, v_field, _window_mean(e_joint), _window_mean(e_series),
+                       _window_mean(e_field), _window_mean(v_series), _window_mean(v_field))
+
+
+def ensemble_joint(values: torch.Tensor, n_samples: int, batch: int, y_true: torch.Tensor, joint: Joint = Joint(),
+                   scale=None) -> JointScores:
+    """The joint scores of ``values`` (T, S*B, R) fp32 (sample n = s*B + b: ``y_hat`` as the solve emits it, or
+    one dynamics channel) against ``y_true`` (B, T, R) over the output indices ``joint`` considers: see
+    ``JointScores``.  ``scale`` as ``ensemble_summary`` takes it.  A HIP tensor runs ude_forecast_joint (one read
+    of the considered values for the energy scores, direct fp64 differences, fixed-order sums; n_samples <= 1024,
+    at most 4096 regions and considered times); a CPU tensor (or no library) the same definitions in torch fp64,
+    in chunks of at most about 256 MB."""
+    if not isinstance(joint, Joint):
+        raise TypeError("ensemble_joint: joint is a Joint")
+    if y_true is None:
+        raise ValueError("ensemble_joint: the joint scores need the targets y_true")
+    T, S, B, R, dev, sc, _q, _nq, lib, yh, yt = _prepare("ensemble_joint", values, n_samples, batch, y_true, scale,
+                                                         None, sorts=True)
+    M = joint.times(T)
+    if lib is None:
+        return _joint_torch(values, S, B, joint, M, y_true, sc)
+    if R > MAX_JOINT_COORDS or M > MAX_JOINT_COORDS:
+        raise ValueError(f"ensemble_joint: at most {MAX_JOINT_COORDS} regions and considered times on the device")
+    opts = (joint.start, joint.every, int(2 * joint.p))
+    with torch.cuda.device(dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        e_joint, e_series, e_field = torch.empty(B, **f64), torch.empty((B, R), **f64), torch.empty((B, M), **f64)
+        v_series, v_field = torch.empty((B, R), **f64), torch.empty((B, M), **f64)
+        means = torch.empty(1 + 2 * R + 2 * M, **f64)
+        ws = torch.empty(lib.forecast_joint_workspace(T, S, B, R, *opts) // 8, **f64)
+        with _fused._timed("forecast_joint"):
+            lib.forecast_joint(T, S, B, R, *opts, yh.data_ptr(), _fused._ptr(sc), yt.data_ptr(), ws.data_ptr(),
+                               e_joint.data_ptr(), e_series.data_ptr(), e_field.data_ptr(), v_series.data_ptr(),
+                               v_field.data_ptr(), means.data_ptr(), _fused._stream(dev))
+    parts = means.split([1, R, M, R, M])
+    return JointScores(e_joint, e_series, e_field, v_series, v_field, parts[0].reshape(()), *parts[1:])
 
 
 GRID_SNAP_ULPS = 8

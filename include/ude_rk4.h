@@ -481,6 +481,33 @@ int ude_forecast_season(int32_t T, int32_t S, int32_t B, int32_t R, int32_t star
                         const float* y_true, const double* q, int32_t n_q, void* ws, double* stats, double* quant,
                         double* peak_time, double* onset, double* overall, double* region, ude_stream_t stream);
 
+/* ude_forecast_joint: the joint scores of y_hat (T, S*B, R) (sample n = s*B + b; no model) against y_true
+ * (B, T, R) -- the proper scores that see how the ensemble's days and regions move together.  Considered
+ * output indices t_m = start + m * every, m = 0 .. M-1, M = ceil((T - start) / every), as ude_forecast_season;
+ * the others are never read.  fp64 after the fp32 load: x_s[m, r] = (double)y_hat[t_m, s*B+b, r] * scale[r],
+ * y[m, r] = (double)y_true[b, t_m, r] * scale[r].  For a window b and a block C of coordinates (m, r), with
+ * |a|_C = sqrt(sum over C of a[m, r]^2) (formed from the differences themselves, never from an expansion of
+ * the square) and p = p_code / 2 (p_code 1: p = 0.5, one sqrt; p_code 2: p = 1, the absolute value),
+ *   ES_C = (1 / S) sum_i |x_i - y|_C - (1 / (2 S^2)) sum_i sum_j |x_i - x_j|_C          (energy score)
+ *   VS_C = sum over c < c' in C of (|y_c - y_c'|^p - (1 / S) sum_s |x_sc - x_sc'|^p)^2   (variogram score,
+ *          unweighted; s ascending; a block of one coordinate: exactly 0)
+ * on the blocks
+ *   series (b, r): the M times of region r     e_series, v_series (B, R)
+ *   field (b, m):  the R regions at time m     e_field, v_field (B, M)
+ *   joint (b):     all M R coordinates         e_joint (B,)   (no variogram: O((M R)^2 S))
+ * means (1 + 2 R + 2 M): the mean over the B windows (b ascending, divided once) of e_joint | e_series (R) |
+ * e_field (M) | v_series (R) | v_field (M).  In one dimension ES is the CRPS; with S = 1 the pair term is
+ * exactly 0.  Fixed-order sums, no atomics: the same bits run to run.  S <= 1024, R <= 4096, M <= 4096,
+ * B <= 65535, start in [0, T), every >= 1, p_code 1 or 2, no null pointer but scale; UDE_E_INVALID otherwise,
+ * before any launch.  ws: ude_forecast_joint_workspace() bytes.  The reference has no counterpart: it replaces
+ * a host copy of the whole (B, S, T, R) prediction and an (S, S, M R) temporary per window. */
+int ude_forecast_joint_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every,
+                                 int32_t p_code, int64_t* ws_bytes);
+int ude_forecast_joint(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start, int32_t every, int32_t p_code,
+                       const float* yhat, const double* scale, const float* y_true, void* ws, double* e_joint,
+                       double* e_series, double* e_field, double* v_series, double* v_field, double* means,
+                       ude_stream_t stream);
+
 /* Library build tag (for logs / tests). */
 const char* ude_build_info(void);
 

@@ -38,12 +38,20 @@ with a table of ones; ``forecast_scn`` with a table in which every (step, region
 (``native_calls_ms``).  On a tree without scenarios only the two solves it has are timed (the yardstick of
 the commit before).
 
+``--joint`` times the joint scores (energy and variogram scores on the series, field and joint blocks) of one
+y_hat (57, 8192, 49) resident on the device, weekly (start 6, every 7) and daily (start 0, every 1), three routes
+taking turns per grid:
+
+  (a) device: ude_amd.forecast.ensemble_joint(...).cpu() -- ude_forecast_joint and one stacked copy;
+  (b) torch on the device: the torch fp64 definitions of the CPU route on the same device tensor;
+  (c) host: a device-to-host copy of y_hat, then the torch fp64 definitions on the host.
+
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
 (ude_amd.fused.EVENTS).  Prints one JSON line.
 
     python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128]
-                                    [--dynamics | --season | --scenario]
+                                    [--dynamics | --season | --scenario | --joint]
 """
 import argparse
 import importlib
@@ -111,6 +119,7 @@ def main():
     ap.add_argument("--dynamics", action="store_true", help="time the dynamics paths instead (see the docstring)")
     ap.add_argument("--season", action="store_true", help="time the seasonal targets instead (see the docstring)")
     ap.add_argument("--scenario", action="store_true", help="time the scenario solve instead (see the docstring)")
+    ap.add_argument("--joint", action="store_true", help="time the joint scores instead (see the docstring)")
     a = ap.parse_args()
     R, B, S, window = 49, a.batch, a.samples, 8
     torch.manual_seed(0)
@@ -215,6 +224,50 @@ def main():
                           "scores_rel_diff_device_vs_host": agree, "histograms_equal": same_hist,
                           "host_route": res_a, "device_route": res_b,
                           "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}))
+        return
+
+    if a.joint:
+        from ude_amd import forecast as fcast
+        from ude_amd import _native
+        T = len(t)
+        with torch.no_grad():
+            yhat = model(x, t, n_samples=S, training=False).permute(2, 1, 0, 3).reshape(T, S * B, R).contiguous()
+        sc = torch.as_tensor(scaler, dtype=torch.float64)
+        out = {"tool": "forecast_timing --joint", "commit": commit_of(), "device": torch.cuda.get_device_name(0),
+               "shape": {"R": R, "S": S, "B": B, "N": S * B, "T": T}, "yhat_bytes": T * S * B * R * 4}
+        for grid, (start, every) in (("weekly", (6, 7)), ("daily", (0, 1))):
+            joint = fcast.Joint(start=start, every=every)
+            M = joint.times(T)
+
+            def device_route(e1=None):
+                js = fcast.ensemble_joint(yhat, S, B, y_test, joint, scale=scaler).cpu()
+                if e1 is not None:
+                    e1.record()
+                return js
+
+            def torch_route(e1=None):
+                js = fcast._joint_torch(yhat, S, B, joint, M, y_test, sc.cuda()).cpu()
+                if e1 is not None:
+                    e1.record()
+                return js
+
+            def host_route(e1=None):
+                v = yhat.cpu()                                                  # the copy the device route saves
+                if e1 is not None:
+                    e1.record()
+                return fcast._joint_torch(v, S, B, joint, M, y_test.cpu(), sc)
+
+            ja, jb = device_route(), torch_route()
+            rel = lambda u, v: float(torch.linalg.vector_norm(u - v) / torch.linalg.vector_norm(v))
+            agree = {name: rel(u, v) for (name, u), (_, v) in zip(ja._tensors(), jb._tensors())}
+            res = timed_alternating([device_route, torch_route, host_route], a.runs, a.warmup)
+            out[grid] = {"M": M, "pair_coordinates": S * S * B * M * R,
+                         "workspace_bytes": _native.prebuilt().forecast_joint_workspace(T, S, B, R, start, every, 1),
+                         "rel_diff_device_vs_torch": agree, "device_route": res[0], "torch_on_device_route": res[1],
+                         "host_route": res[2],
+                         "device_over_torch_on_device_min_wall": res[0]["wall_ms"]["min"] / res[1]["wall_ms"]["min"],
+                         "speedup_vs_host_min_wall": res[2]["wall_ms"]["min"] / res[0]["wall_ms"]["min"]}
+        print(json.dumps(out))
         return
 
     if a.scenario:
