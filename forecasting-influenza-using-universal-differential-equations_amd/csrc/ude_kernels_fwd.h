@@ -93,6 +93,22 @@ __device__ __forceinline__ void store_ckpt_rows(float* blk, const float* lds, in
   }
 }
 
+// How a forward variant's mlp_forward gets its streamed fragments (ude_kernels_mlp.h FS_*): resident weights
+// (WREG, RES, PFB) and the models outside Model::PF_F stream as before; of the others every variant issues its
+// loads in consumption order, and carries them a phase ahead where that compiles without scratch at two
+// workgroups per CU (256 VGPRs).
+template <class M, bool TRAIN, bool DEC, bool DYN, bool SCN, bool RESIDENT>
+constexpr int fwd_stream_mode() {
+  if (RESIDENT || !M::PF_F) return FS_PHASE;
+  if (UDE_ABL == 17) return FS_ABL;
+  // the training DEC forward with stored activations is at the limit already (state49: 249 VGPRs; 36 B of
+  // scratch with the carry): consumption-order loads only
+  if (TRAIN && DEC && M::ACT_STORED) return FS_ORDER;
+  // phase 0 of the first owned net across the flux pass, the other net's at phase 0's head: all of phase 0
+  // (FS_CARRY) spilled in every variant but the inference DEC ones (state49: 72 - 116 B of scratch)
+  return FS_CARRY1;
+}
+
 // ============================================================================
 // Forward solve
 // ============================================================================
@@ -157,6 +173,29 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
   constexpr bool PFB = M::FWD_PFB;
   WRegs<M, W, false, true, RES || PFB> wr;
   if constexpr (!PFB) wr.load(rs, lane);
+  // Streamed fragments (Model::PF_F, weights not resident): issued in the MFMAs' consumption order and, in the
+  // variants with the registers for it, carried a phase ahead (FS_CARRY / FS_CARRY1): phase 0's (state49: 20
+  // quads a wave, or the first net's 10) are issued after each stage's last layer barrier, ahead of the
+  // activation-row copy and the flux pass, whose stores are all younger in vmcnt, so the next stage's first
+  // MFMA waits for neither an L2 round trip nor those stores; phases 1.. are issued by the phase before
+  // (mlp_forward).  The loads issued at a tile's last stage serve the next tile's first (the weights are the
+  // launch's; a workgroup's last issue is never read).  No explicit wait count is needed: the loads and their
+  // first use share the stage loop's body, and the compiler's count at phase 0's first MFMA allows for the
+  // stores and loads issued since (state49 training forward: vmcnt(24); tools/spill_check.py's assembly).
+  // Which variant carries how much is fwd_stream_mode's (registers: profiles/r07/spill_check_r49.txt).
+  constexpr int FSM = fwd_stream_mode<M, TRAIN, DEC, DYN, SCN, decltype(wr)::ON>();
+  constexpr bool CARRY = FSM == FS_CARRY || FSM == FS_CARRY1;
+  f4 fsf[(CARRY && M::WF_Q(W) > 0) ? M::WF_Q(W) : 1], fsb[(CARRY && M::WB_Q(W) > 0) ? M::WB_Q(W) : 1];
+  auto issue_d0 = [&]() {
+    if constexpr (CARRY) {
+      load_phase_frags<M, W, 0, carry0_nets<M, W, FSM>()>(rs, lane, fsf, fsb);
+      __builtin_amdgcn_sched_barrier(0);
+    }
+  };
+  if constexpr (FSM == FS_ABL) {
+    fsf[0] = ldw(rs, lane * 16, 0);
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+  }
   Prof prof_, *pf = nullptr;
 #ifdef UDE_PROFILE
   if (TRAIN && A.prof && tid == 0) {
@@ -169,6 +208,7 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
   #pragma unroll 1
   for (int i = tid; i < TT * SR; i += NTHREADS) lds[i] = 0.f;
   lds_sync();
+  issue_d0();                                     // the first tile's first stage
 
   for (int tile = blockIdx.x; tile < A.n_tiles; tile += gridDim.x) {
     const int n0 = tile * TT;
@@ -352,7 +392,8 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
             if constexpr (TRAIN && CKR)
               store_ckpt_rows<M, SR>(A.ckpt + ckpt_index(tile, A.n_steps, step, j, M::F, 0, 0), lds, tid);
           }
-        });
+        }, std::integral_constant<int, FSM>{}, fsf, fsb);
+        issue_d0();                                // the next stage's phase 0 (FS_CARRY), ahead of every store below
         if constexpr (PFB) {
           const int en = 4 * step + j + 1;
           if (en < 4 * A.n_steps) wr.load(make_rsrc(A.pack + (size_t)en * M::PACK_TOTAL, M::PACK_TOTAL * 4), lane, false);
@@ -524,7 +565,8 @@ __device__ void fwd_body(const KArgs& A, float* lds) {
       const int last = A.n_steps - 1;
       if (sc.out_start[last] < sc.out_start[last + 1]) {
         const int jo = sc.out_j[sc.out_start[last]];
-        mlp_forward<M, W, SR>(rs, lds, c1, lane, wr, pf);
+        mlp_forward<M, W, SR>(rs, lds, c1, lane, wr, pf, NoHook{}, std::integral_constant<int, FSM>{}, fsf, fsb);
+        issue_d0();                              // FS_CARRY: this call consumed the next tile's
         dyn_pass(jo, last);                      // SCN: the last step's row
         lds_sync();
       }

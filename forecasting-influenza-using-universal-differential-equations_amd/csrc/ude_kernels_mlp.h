@@ -235,17 +235,171 @@ struct NoHook {
   __device__ __forceinline__ void operator()(D) const {}
 };
 
+// Phase d's streamed forward fragments and bias quads of wave W, issued in the order the phase's MFMAs
+// consume them (per net: the owned tiles' bias quads, then K quad by K quad across the tiles that share
+// the B operand), so the first MFMA of the phase waits for the first load only.  fr: [FQ(W, d)] at
+// fq_before(W, d, k) + q; bs: [nb_phase(W, d)] at nb_before(W, d, k).  NETS: bit n set = net n's tiles.
+template <class M, int W, int d, int NETS = 3>
+__device__ __forceinline__ void load_phase_frags(Rsrc rs, int lane, f4* fr, f4* bs) {
+  const int g = lane >> 4;
+  sfor<2>([&](auto nn) {
+    constexpr int net = decltype(nn)::value;
+    if constexpr (M::owns_f(W, d, net) && ((NETS >> net) & 1)) {
+      constexpr int NQ = M::kin(net, d) / 16;
+      if constexpr (M::has_bias(d))
+        sfor<M::FT(d)>([&](auto kk) {
+          constexpr int k = decltype(kk)::value;
+          if constexpr (M::fowner(d, k) == W && M::fnet(d, k) == net)
+            bs[M::nb_before(W, d, k)] = ldw(rs, g * 16, (M::b_off(net, d) + M::frt(d, k) * 16) * 4);
+        });
+      sfor<NQ>([&](auto qq) {
+        constexpr int q = decltype(qq)::value;
+        sfor<M::FT(d)>([&](auto kk) {
+          constexpr int k = decltype(kk)::value;
+          if constexpr (M::fowner(d, k) == W && M::fnet(d, k) == net)
+            fr[M::fq_before(W, d, k) + q] =
+                ldw(rs, lane * 16, (M::wf_off(net, d) + M::frt(d, k) * NQ * 256 + q * 256) * 4);
+        });
+      });
+    }
+  });
+}
+
+// How mlp_forward gets the fragments it streams from L2 (weights not register-resident):
+//   FS_PHASE  each phase issues its own at its head, tile by tile, and its MFMAs wait for them;
+//   FS_ORDER  the same, issued in the MFMAs' consumption order (load_phase_frags);
+//   FS_CARRY  (Model::PF_F) every phase finds its fragments in flight: they live in the caller's arrays
+//             (`fsf` [WF_Q(W)], `fsb` [WB_Q(W)], WRegs' layout), the caller issues phase 0's ahead of the call
+//             and phase d issues phase d + 1's;
+//   FS_CARRY1 as FS_CARRY, but of phase 0 the caller issues only the tiles of the first net the wave owns
+//             (carry0_nets) and phase 0 the other net's at its head: half the registers across the caller's
+//             code, and the second net's MFMAs start a whole net's chain after their loads;
+//   FS_ABL    timing ablation (UDE_ABL 17): every fragment and bias quad is fsf[0], nothing is loaded.
+enum : int { FS_PHASE = 0, FS_ORDER = 1, FS_CARRY = 2, FS_ABL = 3, FS_CARRY1 = 4 };
+// the nets (bit mask) whose phase-0 tiles of wave W the caller issues ahead of mlp_forward
+template <class M, int W, int FSM>
+constexpr int carry0_nets() {
+  if (FSM == FS_CARRY) return 3;
+  if (FSM == FS_CARRY1) return M::owns_f(W, 0, 0) ? 1 : 2;
+  return 0;
+}
+
+// One phase of mlp_forward in the FS_ORDER / FS_CARRY / FS_ABL modes (see there), up to its barrier.
+template <class M, int W, int SR, int d, int FSM, class Hook>
+__device__ __forceinline__ void mlp_forward_phase_fs(Rsrc rs, float* rec, const f4* c1, int lane, const Hook& hook,
+                                                     f4* fsf, f4* fsb) {
+  constexpr int NF = M::FQ(W, d), NB = M::nb_phase(W, d);
+  static_assert(NF <= 24 && !(d == 0 && pack0_w<M, W>()), "Model::PF_F: no chunked and no packed layer 0");
+  const int g = lane >> 4;
+  constexpr bool CARRY = FSM == FS_CARRY || FSM == FS_CARRY1, OWN = FSM == FS_ORDER;
+  f4 frl[(OWN && NF > 0) ? NF : 1], bsl[(OWN && NB > 0) ? NB : 1];
+  const f4* fr = CARRY ? fsf + M::fq_base(W, d) : frl;
+  const f4* bs = CARRY ? fsb + M::nb_base(W, d) : bsl;
+  if constexpr (OWN) load_phase_frags<M, W, d>(rs, lane, frl, bsl);
+  // FS_CARRY: the next phase's fragments go out at this phase's head, next to this phase's own (in flight
+  // since the phase before).  Phase 0 carries the most (state49: 20 quads), so phase 1's are issued
+  // inside it, once the first net's MFMAs have freed that net's fragments -- where a wave owns tiles of both
+  // nets; else behind the phase's MFMAs.
+  constexpr bool NEXT = CARRY && d + 1 < M::D;
+  constexpr bool MID0 = d == 0 && M::owns_f(W, 0, 0) && M::owns_f(W, 0, 1);
+  auto issue_next = [&]() {
+    if constexpr (NEXT) load_phase_frags<M, W, (NEXT ? d + 1 : d)>(rs, lane, fsf + M::fq_base(W, d + 1),
+                                                                  fsb + M::nb_base(W, d + 1));
+  };
+  if constexpr (d > 0) issue_next();
+  if constexpr (d == 0 && CARRY) load_phase_frags<M, W, 0, 3 & ~carry0_nets<M, W, FSM>()>(rs, lane, fsf, fsb);
+  if constexpr (!(CARRY && MID0)) hook(std::integral_constant<int, d>{});
+  __builtin_amdgcn_sched_barrier(0);
+  auto FR = [&](int i) -> f4 {
+    if constexpr (FSM == FS_ABL) return fsf[0];
+    else return fr[i];
+  };
+  f4 acc[M::FT(d) > 0 ? M::FT(d) : 1];
+  sfor<M::FT(d)>([&](auto kk) {
+    constexpr int k = decltype(kk)::value;
+    if constexpr (M::fowner(d, k) == W) {
+      if constexpr (d == 0 && M::HOIST) acc[k] = c1[M::nz_before(W, k)];
+      else if constexpr (FSM == FS_ABL) acc[k] = fsf[0];
+      else acc[k] = bs[M::nb_before(W, d, k)];
+    }
+  });
+  // as mlp_forward: the wave's tiles of one net share the B operand, read QB quads ahead of their MFMAs
+  sfor<2>([&](auto nn) {
+    constexpr int net = decltype(nn)::value;
+    if constexpr (M::owns_f(W, d, net)) {
+      constexpr int KP = M::kin(net, d);
+      constexpr int inoff = d == 0 ? M::Y_OFF : M::act_off(net, d - 1);
+      const float* b = rec + inoff + g * (KP / 4);
+      constexpr int NQ = KP / 16, QB = 5;
+#pragma unroll
+      for (int q0 = 0; q0 < NQ; q0 += QB) {
+        f4 xb[QB];
+#pragma unroll
+        for (int q = q0; q < q0 + QB && q < NQ; ++q) xb[q - q0] = *reinterpret_cast<const f4*>(b + 4 * q);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int q = q0; q < q0 + QB && q < NQ; ++q) {
+          const f4 x = xb[q - q0];
+#pragma unroll
+          for (int e = 0; e < 4; ++e)
+            sfor<M::FT(d)>([&](auto kk) {
+              constexpr int k = decltype(kk)::value;
+              if constexpr (M::fowner(d, k) == W && M::fnet(d, k) == net) {
+                const f4 wq = FR(M::fq_before(W, d, k) + q);
+                if constexpr (UDE_ABL == 13) acc[k][e] += x[e];
+                else acc[k] = mfma4(wq[e], x[e], acc[k]);
+              }
+            });
+        }
+      }
+      if constexpr (CARRY && MID0 && net == 0) {
+        // the stage-input checkpoint rows still go out behind the loads (see fwd_body)
+        __builtin_amdgcn_sched_barrier(0);
+        issue_next();
+        hook(std::integral_constant<int, d>{});
+        __builtin_amdgcn_sched_barrier(0);
+      }
+    }
+  });
+  if constexpr (d == 0 && !MID0) {
+    __builtin_amdgcn_sched_barrier(0);
+    issue_next();
+    __builtin_amdgcn_sched_barrier(0);
+  }
+  sfor<M::FT(d)>([&](auto kk) {
+    constexpr int k = decltype(kk)::value;
+    if constexpr (M::fowner(d, k) == W) {
+      constexpr int net = M::fnet(d, k), rt = M::frt(d, k);
+      f4 a = acc[k];
+      if constexpr (M::act(net, d)) {
+        a[0] = elu1(a[0]); a[1] = elu1(a[1]);
+        a[2] = elu1(a[2]); a[3] = elu1(a[3]);
+      }
+      *reinterpret_cast<f4*>(rec + M::act_off(net, d) + rt * 16 + g * 4) = a;
+    }
+  });
+}
+
 // `hook(integral_constant<d>)` runs right after phase d's weight loads are issued
 // (used by the backward to start HBM loads early without holding registers long).
-template <class M, int W, int SR, class WR = NoWRegs, class Hook = NoHook>
+template <class M, int W, int SR, class WR = NoWRegs, class Hook = NoHook, int FSM = FS_PHASE>
 __device__ __forceinline__ void mlp_forward(Rsrc rs, float* lds, const f4* c1, int lane, const WR& wr = WR{},
-                                            Prof* pf = nullptr, const Hook& hook = Hook{}) {
+                                            Prof* pf = nullptr, const Hook& hook = Hook{},
+                                            std::integral_constant<int, FSM> = {}, f4* fsf = nullptr,
+                                            f4* fsb = nullptr) {
   constexpr bool RW = WR::ON;
+  static_assert(FSM == FS_PHASE || !RW, "resident fragments are not streamed");
   const int t = lane & 15, g = lane >> 4;
   float* rec = lds + t * SR;
   sfor<M::D>([&](auto dd) {
     constexpr int d = decltype(dd)::value;
     constexpr int NF = M::FQ(W, d);
+    if constexpr (FSM != FS_PHASE) {
+      mlp_forward_phase_fs<M, W, SR, d, FSM>(rs, rec, c1, lane, hook, fsf, fsb);
+      lds_sync();
+      UDE_STAMP(pf, 2 + d);
+      return;
+    }
     // all of this wave's weight fragments (and biases) for the phase are in flight
     // before its first MFMA -- unless they would not fit next to the working set (the Bayesian
     // state model's layer 0, K = 416: 208 VGPRs, spilled at the forward's 256): then chunk by chunk

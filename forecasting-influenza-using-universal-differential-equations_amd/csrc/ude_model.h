@@ -401,6 +401,21 @@ struct Model {
   // during the previous evaluation's flux pass (fwd_body PFB)
   static constexpr bool FWD_PFB = BAYES &&
                                   cmax(cmax(fwd_wreg_q(0), fwd_wreg_q(1)), cmax(fwd_wreg_q(2), fwd_wreg_q(3))) <= 40;
+  // Deterministic forward of a large record (several pair slots per thread: two 4-wave workgroups per CU at
+  // any batch) that streams its fragments from L2 (not register-resident, no chunked and no packed layer 0):
+  // the loads go out in the order the MFMAs consume them and, where the kernel variant has the registers
+  // (fwd_stream_mode), a phase ahead of them.  -DUDE_FWD_STREAM=0: each phase issues its own fragments tile
+  // by tile at its head, as before (A/B measurements, tests/test_fwd_stream_gpu.py).
+#ifndef UDE_FWD_STREAM
+#define UDE_FWD_STREAM 1
+#endif
+  static constexpr int max_fq() {
+    int m = 0;
+    for (int w = 0; w < WAVES; ++w)
+      for (int d = 0; d < D; ++d) m = cmax(m, FQ(w, d));
+    return m;
+  }
+  static constexpr bool PF_F = UDE_FWD_STREAM != 0 && !BAYES && !WREG && SLOTS_ > 1 && max_fq() <= 24;
 
   // ---- parameters in torch order (nn.Linear weight (out,in) then bias) ----------------
   static constexpr int param_w_off(int net, int i) {

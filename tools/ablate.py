@@ -9,7 +9,8 @@ GPU box, each library is timed on the bench's M1 backward and the per-variant ke
   large records (ABL_WORKLOAD=state49): 21 no partner dW MFMAs  22 no activation-row LDS-DMA
   8 no stage-start activation load (4-wave large path)  12 / 11 / 13 forward ablations (no flux pass /
   no activation-row stores / no layer MFMAs)  14 / 15 / 16 forward flux pass: no fp64 side sums / no
-  stage-input checkpoint stores / no latent output stores
+  stage-input checkpoint stores / no latent output stores  17 forward: no streamed weight loads (every fragment
+  and bias quad of mlp_forward is one quad loaded once per launch)
 """
 import importlib
 import os
