@@ -8,6 +8,7 @@
 #include "ude_forecast.h" // model-independent ensemble summary kernels (likewise)
 #include "ude_season.h"   // model-independent seasonal-target kernels (likewise)
 #include "ude_joint.h"    // model-independent energy / variogram score kernels (likewise)
+#include "ude_aggregate.h" // model-independent aggregation over the regions (likewise)
 
 // This translation unit is host code only (no kernels are instantiated here).
 #if !defined(__HIP_DEVICE_COMPILE__)
@@ -363,6 +364,16 @@ int ude_forecast_joint(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start
                        ude_stream_t stream) {
   return ude::forecast_joint(T, S, B, R, start, every, p_code, yhat, scale, y_true, ws, e_joint, e_series, e_field,
                              v_series, v_field, means, (hipStream_t)stream);
+}
+
+int ude_forecast_aggregate(int64_t rows, int32_t R, int32_t n_levels, const int32_t* g_off, const float* x,
+                           const double* scale, const double* w, float* out, ude_stream_t stream) {
+  return ude::forecast_aggregate(rows, R, n_levels, g_off, x, scale, w, out, (hipStream_t)stream);
+}
+
+int ude_forecast_aggregate_dyn(int32_t kind, int64_t rows, int32_t R, int32_t n_levels, const int32_t* g_off,
+                               const float* dyn, const double* w, float* out, ude_stream_t stream) {
+  return ude::forecast_aggregate_dyn(kind, rows, R, n_levels, g_off, dyn, w, out, (hipStream_t)stream);
 }
 
 #ifdef UDE_PROFILE

@@ -211,7 +211,7 @@ class VAE:
         return y_pred
 
     def forecast(self, x, t, n_samples=128, y_true=None, scaler=None, quantiles=None, verify=None, dynamics=False,
-                 season=None, scenarios=None, joint=None):
+                 season=None, scenarios=None, joint=None, aggregate=None):
         """Ensemble forecast of the windows ``x`` at the times ``t``: an ``ude_amd.forecast.Forecast``
         (per (window, day, region) mean / std over the ``n_samples`` trajectories of the data scaled
         by ``scaler`` -- something with ``.values`` or array-like, as ``evaluate`` takes -- optional
@@ -254,7 +254,20 @@ class VAE:
         (``ude_amd.forecast.JointScores``): the energy and variogram scores of each window's trajectories
         against ``y_true`` (required), which see the dependence between days and between regions that no
         per-day score does, from the same prediction on every route (ude_forecast_joint on the device).
-        Scenarios get none: the observation did not happen under them.  With ``joint=None`` nothing changes."""
+        Scenarios get none: the observation did not happen under them.  With ``joint=None`` nothing changes.
+
+        ``aggregate`` -- a mapping name -> ``ude_amd.forecast.Aggregate`` (a weight matrix over the regions: the
+        HHS regions, the nation) -- also fills ``Forecast.aggregates[name]`` with a whole ``Forecast`` of that
+        level, on every route: the prediction, the targets and (with ``dynamics``) the dynamics are summed over
+        the regions trajectory by trajectory, so a level's spread carries how the regions move together
+        (ude_forecast_aggregate / ude_forecast_aggregate_dyn on the device, one call each for all levels; the
+        prediction is still not copied to the host), and every level's ensemble then goes through the same
+        summaries as the baseline -- ``quantiles``, ``verify``, ``dynamics``, ``season`` (with the level's own
+        ``baseline``) and ``joint``.  Each scenario's ``forecast`` and ``effect`` get ``aggregates`` too (the
+        summary of the aggregated scenario prediction and of the aggregated paired difference).  With
+        ``aggregate=None`` nothing changes."""
+        if aggregate is not None:
+            aggregate = ude_forecast.check_levels("forecast", aggregate, self.n_regions)
         if joint is True:
             joint = ude_forecast.Joint()
         if joint is not None:
@@ -322,12 +335,17 @@ class VAE:
                                                      quantiles=quantiles)
         if joint is not None:
             fc.joint = ude_forecast.ensemble_joint(yhat, n_samples, B, y_true, joint, scale=scaler)
+        if aggregate is not None:
+            fc.aggregates = ude_forecast.aggregate_forecasts(aggregate, yhat, n_samples, B, y_true=y_true, scale=scaler,
+                                                             quantiles=quantiles, verify=verify,
+                                                             dyn=dyn if dynamics else None, season=season, joint=joint)
         if scenarios is not None:
             fc.scenarios = {name: self._forecast_scenario(sc, z, t, yhat, n_samples, B, scaler, quantiles, dynamics,
-                                                          season) for name, sc in scenarios.items()}
+                                                          season, aggregate) for name, sc in scenarios.items()}
         return fc
 
-    def _forecast_scenario(self, scenario, z, t, yhat, n_samples, B, scaler, quantiles, dynamics, season):
+    def _forecast_scenario(self, scenario, z, t, yhat, n_samples, B, scaler, quantiles, dynamics, season,
+                           aggregate=None):
         """One ``ScenarioForecast`` of ``forecast``: the scenario solved on the baseline's ``z``, its own
         summaries, and the summaries of the paired difference to the baseline's ``yhat``."""
         step = t[1] - t[0]
@@ -353,6 +371,11 @@ class VAE:
                 out.dynamics = ude_forecast.dynamics_summary(dyn, names, n_samples, B, quantiles=quantiles)
             diff = yhat_s - yhat.detach()
             effect = ude_forecast.ensemble_summary(diff, n_samples, B, scale=scaler, quantiles=quantiles)
+            if aggregate is not None:
+                out.aggregates = ude_forecast.aggregate_forecasts(aggregate, yhat_s, n_samples, B, scale=scaler,
+                                                                  quantiles=quantiles)
+                effect.aggregates = ude_forecast.aggregate_forecasts(aggregate, diff, n_samples, B, scale=scaler,
+                                                                     quantiles=quantiles)
             effect_season = None
             if season is not None:
                 out.season = ude_forecast.ensemble_season(yhat_s, n_samples, B, season, scale=scaler,

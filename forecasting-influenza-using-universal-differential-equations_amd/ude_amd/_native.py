@@ -166,6 +166,8 @@ _CABI: Dict[str, tuple] = {
     "ude_forecast_season": _sig("forecast_season", (8, _i32), (5, _vp), _i32, (8, _vp)),
     "ude_forecast_joint_workspace": _sig(None, (7, _i32), _pi64),
     "ude_forecast_joint": _sig("forecast_joint", (7, _i32), (11, _vp)),
+    "ude_forecast_aggregate": _sig("forecast_aggregate", _i64, (2, _i32), (6, _vp)),
+    "ude_forecast_aggregate_dyn": _sig("forecast_aggregate_dyn", _i32, _i64, (2, _i32), (5, _vp)),
     "ude_build_info": _sig(None),
 }
 EXPORTED_SYMBOLS = tuple(_CABI)

@@ -40,6 +40,13 @@ own summaries and those of the paired difference to the baseline, solved on the 
 score of a window's S trajectories against the observed one, on region r's series, on the field of the
 regions at one time and on all considered coordinates at once -- the scores that tell an ensemble whose days
 and regions move together from one with the same marginals that does not -- as a ``JointScores``.
+
+``Aggregate`` is a level of a hierarchy over the regions (the HHS regions, the nation): ``ensemble_aggregate``
+sums ``y_hat`` over the regions with the level's weights trajectory by trajectory (ude_forecast_aggregate: one
+read for all levels, fp64 in a stated order, stored as fp32), ``aggregate_dynamics`` the dynamics
+(ude_forecast_aggregate_dyn: the aggregate's own beta, gamma and R_eff from its infections and recoveries), and
+``VAE.forecast(aggregate={...})`` returns per level a whole ``Forecast`` of that coherent ensemble in
+``Forecast.aggregates``.
 """
 from __future__ import annotations
 
@@ -156,10 +163,98 @@ class Joint:
         return -((self.start - T) // self.every)
 
 
+MAX_AGGREGATE_REGIONS = 4096             # AG_MAX_R (csrc/ude_aggregate.h): the device's limits
+MAX_AGGREGATE_GROUPS = 256               # AG_MAX_G, over all levels
+MAX_AGGREGATE_LEVELS = 16                # AG_MAX_LEVELS
+
+
+@dataclass(frozen=True, eq=False)
+class Aggregate:
+    """One level of a hierarchy over the regions: ``weights`` (G, R), finite, any sign -- group g of the level
+    is ``sum_r weights[g, r] * value_r``, trajectory by trajectory (population shares: rows that sum to 1).
+    ``names``: None or one name per group.  ``baseline``: None, a number or one per group, in data units -- the
+    onset baseline ``VAE.forecast(season=...)`` uses at this level (None: no onset there)."""
+    weights: object
+    names: Optional[Tuple[str, ...]] = None
+    baseline: Optional[object] = None
+
+    def __post_init__(self):
+        w = self.weights
+        if isinstance(w, torch.Tensor):
+            w = w.detach().cpu().numpy()
+        try:
+            w = np.array(w.values if hasattr(w, "values") else w, dtype=np.float64)
+        except (TypeError, ValueError) as e:
+            raise ValueError("Aggregate: weights are not numeric") from e
+        if w.ndim != 2 or w.shape[0] < 1 or w.shape[1] < 1 or not np.isfinite(w).all():
+            raise ValueError(f"Aggregate: weights are a finite (G, R) matrix, not {w.shape}")
+        w.setflags(write=False)
+        object.__setattr__(self, "weights", w)
+        if self.names is not None:
+            names = tuple(self.names)
+            if len(names) != w.shape[0]:
+                raise ValueError(f"Aggregate: {len(names)} names for {w.shape[0]} groups")
+            object.__setattr__(self, "names", names)
+        if self.baseline is not None:
+            try:
+                base = np.asarray(self.baseline.values if hasattr(self.baseline, "values") else self.baseline,
+                                  dtype=np.float64)
+            except (TypeError, ValueError) as e:
+                raise ValueError("Aggregate: baseline is not numeric") from e
+            if base.ndim > 1 or base.size not in (1, w.shape[0]) or not np.isfinite(base).all():
+                raise ValueError(f"Aggregate: baseline is a finite number or one per group ({w.shape[0]})")
+            object.__setattr__(self, "baseline", float(base) if base.ndim == 0 else tuple(base.tolist()))
+
+    def on(self, device) -> torch.Tensor:
+        """The weights as an fp64 tensor on ``device``, copied there once."""
+        cache = self.__dict__.setdefault("_on", {})
+        key = str(torch.device(device))
+        if key not in cache:
+            cache[key] = torch.from_numpy(np.array(self.weights)).to(device)
+        return cache[key]
+
+    @property
+    def n_groups(self) -> int:
+        return self.weights.shape[0]
+
+    @property
+    def n_regions(self) -> int:
+        return self.weights.shape[1]
+
+    @classmethod
+    def from_groups(cls, R: int, groups, share, names=None, baseline=None) -> "Aggregate":
+        """The level whose group g holds the regions ``groups[g]`` weighted by their share of the group:
+        ``a[g, r] = share[r] / sum_{r' in groups[g]} share[r']`` for r in the group, else 0.  ``share``: one
+        non-negative value per region (populations); each group's shares must sum to more than 0."""
+        if isinstance(R, bool) or int(R) != R or int(R) < 1:
+            raise ValueError(f"Aggregate.from_groups: R {R!r} (at least one region)")
+        R = int(R)
+        try:
+            sh = np.asarray(share.values if hasattr(share, "values") else share, dtype=np.float64).reshape(-1)
+        except (TypeError, ValueError) as e:
+            raise ValueError("Aggregate.from_groups: share is not numeric") from e
+        if sh.shape != (R,) or not np.isfinite(sh).all() or (sh < 0).any():
+            raise ValueError(f"Aggregate.from_groups: share is one finite value >= 0 per region ({R})")
+        groups = [list(g) for g in groups]
+        if not groups:
+            raise ValueError("Aggregate.from_groups: no group")
+        a = np.zeros((len(groups), R))
+        for g, members in enumerate(groups):
+            if not members or any(isinstance(r, bool) or int(r) != r or not 0 <= int(r) < R for r in members) \
+                    or len(set(int(r) for r in members)) != len(members):
+                raise ValueError(f"Aggregate.from_groups: group {g} is a set of region indices in [0, {R})")
+            idx = [int(r) for r in members]
+            total = sh[idx].sum()
+            if not total > 0:
+                raise ValueError(f"Aggregate.from_groups: the shares of group {g} sum to {total}")
+            a[g, idx] = sh[idx] / total
+        return cls(a, names, baseline)
+
+
 class _Result:
     """What the result containers (dataclasses) share.  A field holds a tensor, None, another container
     (``Forecast.dynamics`` / ``.season`` / ``.joint``: handled by recursion), a dict of containers by name
-    (``Forecast.scenarios``: each in its place, in the dict's order) or something else that is carried
+    (``Forecast.scenarios`` / ``.aggregates``: each in its place, in the dict's order) or something else that is carried
     through (``Dynamics.names``)."""
 
     def _tensors(self):
@@ -310,7 +405,10 @@ class Forecast(_Result):
     (``VAE.forecast(dynamics=True)``), else None.  ``season``: its ``SeasonTargets``
     (``VAE.forecast(season=Season(...))``), else None.  ``scenarios``: name -> ``ScenarioForecast`` of
     every scenario solved beside it on the same draw (``VAE.forecast(scenarios={...})``), else None.
-    ``joint``: its ``JointScores`` (``VAE.forecast(joint=True)`` or a ``Joint``), else None."""
+    ``joint``: its ``JointScores`` (``VAE.forecast(joint=True)`` or a ``Joint``), else None.
+    ``aggregates``: name -> the ``Forecast`` of that level of ``VAE.forecast(aggregate={...})`` -- the same
+    fields with the level's G groups in place of the R regions --, else None (declared before ``joint``, which
+    stays the last field)."""
     mean: torch.Tensor
     std: torch.Tensor
     quantiles: Optional[torch.Tensor] = None
@@ -332,6 +430,7 @@ class Forecast(_Result):
     dynamics: Optional[Dynamics] = None
     season: Optional[SeasonTargets] = None
     scenarios: Optional[Dict[str, "ScenarioForecast"]] = None
+    aggregates: Optional[Dict[str, "Forecast"]] = None
     joint: Optional[JointScores] = None
 
 
@@ -880,6 +979,154 @@ def ensemble_joint(values: torch.Tensor, n_samples: int, batch: int, y_true: tor
                                v_field.data_ptr(), means.data_ptr(), _fused._stream(dev))
     parts = means.split([1, R, M, R, M])
     return JointScores(e_joint, e_series, e_field, v_series, v_field, parts[0].reshape(()), *parts[1:])
+
+
+def check_levels(who: str, levels, R: Optional[int] = None) -> Dict[str, Aggregate]:
+    """``levels`` as a dict name -> ``Aggregate`` (TypeError for anything else, ValueError for none or, with
+    ``R``, for a level whose weights have another number of regions)."""
+    if not hasattr(levels, "items"):
+        raise TypeError(f"{who}: the levels are a mapping name -> ude_amd.forecast.Aggregate")
+    levels = dict(levels.items())
+    for name, lv in levels.items():
+        if not isinstance(lv, Aggregate):
+            raise TypeError(f"{who}: level {name!r} is not an ude_amd.forecast.Aggregate")
+        if R is not None and lv.n_regions != R:
+            raise ValueError(f"{who}: level {name!r} has weights for {lv.n_regions} regions, the values have {R}")
+    if not levels:
+        raise ValueError(f"{who}: no level")
+    return levels
+
+
+def _stack_levels(who: str, levels, R: int, dev, native: bool):
+    """``(levels, w (G_tot, R) fp64 on dev, g_off)``: the levels' rows stacked in the mapping's order, level l's
+    first row ``g_off[l]``; with ``native`` the device's limits hold."""
+    levels = check_levels(who, levels, R)
+    g_off = [0]
+    for lv in levels.values():
+        g_off.append(g_off[-1] + lv.n_groups)
+    if native and (R > MAX_AGGREGATE_REGIONS or g_off[-1] > MAX_AGGREGATE_GROUPS or len(levels) > MAX_AGGREGATE_LEVELS):
+        raise ValueError(f"{who}: at most {MAX_AGGREGATE_REGIONS} regions, {MAX_AGGREGATE_GROUPS} groups over all "
+                         f"levels and {MAX_AGGREGATE_LEVELS} levels on the device")
+    return levels, torch.cat([lv.on(dev) for lv in levels.values()]).contiguous(), g_off
+
+
+def _weighted_sums(v: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
+    """``acc = 0; acc = acc + w[:, r] * v[..., r]`` for r ascending: v (..., R) fp64, w (G, R) -> (..., G) fp64.
+    Elementwise, so every product and sum is rounded on its own in the order the kernel has."""
+    acc = torch.zeros(v.shape[:-1] + (w.shape[0],), dtype=torch.float64, device=v.device)
+    for r in range(v.shape[-1]):
+        acc = acc + w[:, r] * v[..., r, None]
+    return acc
+
+
+def ensemble_aggregate(values: torch.Tensor, levels, scale=None) -> Dict[str, torch.Tensor]:
+    """The weighted sums over the regions of ``values`` (..., R) (read as fp32; any leading dimensions: ``y_hat``
+    (T, S*B, R), targets (B, T, R)) for every level of ``levels``, a mapping name -> ``Aggregate``: a dict name
+    -> fp32 tensor (..., G_l).  Per element of the leading dimensions and group g, in fp64: ``acc = 0``, then
+    ``acc = acc + w[g, r] * (values[..., r] * scale[r])`` for r ascending, every product and sum rounded on its own,
+    stored as fp32 -- the aggregated ensemble is that fp32 array, which ``ensemble_summary`` and the others read
+    with ``scale=None``.  A HIP tensor runs ude_forecast_aggregate, one call and one read of ``values`` for all
+    levels (at most 4096 regions, 256 groups in all, 16 levels); a CPU tensor (or no library) the same operations
+    in torch fp64, r by r: the same bits."""
+    if values.dim() < 1 or values.shape[-1] < 1:
+        raise ValueError(f"ensemble_aggregate: values {tuple(values.shape)} are not (..., R)")
+    R, lead = int(values.shape[-1]), tuple(values.shape[:-1])
+    dev = values.device
+    lib = _library() if values.is_cuda else None
+    levels, w, g_off = _stack_levels("ensemble_aggregate", levels, R, dev, lib is not None)
+    sc = _scale_vector(scale, R, dev)
+    x = values.detach().to(torch.float32)
+    if lib is None:
+        v = x.to(torch.float64)
+        if sc is not None:
+            v = v * sc
+        acc = _weighted_sums(v, w).to(torch.float32)
+        return {name: acc[..., g_off[l]:g_off[l + 1]].contiguous() for l, name in enumerate(levels)}
+    x = x.contiguous()
+    rows = x.numel() // R
+    with torch.cuda.device(dev):
+        out = torch.empty(rows * g_off[-1], dtype=torch.float32, device=dev)
+        if rows:                                 # an empty tensor has no address to hand over
+            with _fused._timed("forecast_aggregate"):
+                lib.forecast_aggregate(rows, R, len(levels), _i32_array(g_off), x.data_ptr(), _fused._ptr(sc),
+                                       w.data_ptr(), out.data_ptr(), _fused._stream(dev))
+    return {name: out[rows * g_off[l]:rows * g_off[l + 1]].view(*lead, g_off[l + 1] - g_off[l])
+            for l, name in enumerate(levels)}
+
+
+def _i32_array(v: Sequence[int]):
+    import ctypes
+    return (ctypes.c_int32 * len(v))(*v)
+
+
+def aggregate_dynamics(dyn: torch.Tensor, names: Sequence[str], levels) -> Dict[str, Tuple[torch.Tensor, Tuple[str, ...]]]:
+    """The dynamics ``dyn`` (C, T, N, R) (read as fp32; the channels ``names`` of ``dynamics_names``) of every
+    level of ``levels``: a dict name -> ``(dyn_l (C, T, N, G_l) fp32, names)``.  With the summation of
+    ``ensemble_aggregate`` (fp64, r ascending, no scale): s, i, r and fa_* are the weighted sums; with ``inc =
+    sum w (beta s) i`` and ``rec = sum w gamma i``, the aggregate's new infections and recoveries per unit time,
+    ``beta = inc / (s i)``, ``gamma = rec / i`` and ``r_eff = inc / rec`` of the aggregate's own s and i -- the
+    rates one SIR population with the aggregate's S and I would need, so ``r_eff = beta s / gamma``; the regional
+    ``r_eff`` is not read (its mean is not the aggregate's reproduction number).  Plain IEEE divisions (i = 0:
+    inf or NaN), each channel rounded once to fp32.  A HIP tensor runs ude_forecast_aggregate_dyn, one call for
+    all levels; a CPU tensor (or no library) the same operations in torch fp64."""
+    names = tuple(names)
+    rates, flux = "beta" in names, "fa_s" in names
+    if dyn.dim() != 4 or names != DYN_STATE + (DYN_RATES if rates else ()) + (DYN_FLUX if flux else ()) \
+            or dyn.shape[0] != len(names) or not (rates or flux):
+        raise ValueError(f"aggregate_dynamics: dyn {tuple(dyn.shape)} is not (C, T, N, R) with the channels of "
+                         f"dynamics_names, {names}")
+    C, T, N, R = (int(v) for v in dyn.shape)
+    dev = dyn.device
+    lib = _library() if dyn.is_cuda else None
+    levels, w, g_off = _stack_levels("aggregate_dynamics", levels, R, dev, lib is not None)
+    x = dyn.detach().to(torch.float32)
+    if lib is None:
+        v = x.to(torch.float64)
+        ch = {n: _weighted_sums(v[c], w) for c, n in enumerate(names) if n != "r_eff" and n not in ("beta", "gamma")}
+        if rates:
+            s, i, beta, gamma = v[0], v[1], v[names.index("beta")], v[names.index("gamma")]
+            inc, rec = _weighted_sums((beta * s) * i, w), _weighted_sums(gamma * i, w)
+            ch["beta"], ch["gamma"], ch["r_eff"] = inc / (ch["s"] * ch["i"]), rec / ch["i"], inc / rec
+        acc = torch.stack([ch[n] for n in names]).to(torch.float32)
+        return {name: (acc[..., g_off[l]:g_off[l + 1]].contiguous(), names) for l, name in enumerate(levels)}
+    x = x.contiguous()
+    rows = T * N
+    kind = (1 if rates else 0) | (2 if flux else 0)
+    with torch.cuda.device(dev):
+        out = torch.empty(C * rows * g_off[-1], dtype=torch.float32, device=dev)
+        if rows:
+            with _fused._timed("forecast_aggregate_dyn"):
+                lib.forecast_aggregate_dyn(kind, rows, R, len(levels), _i32_array(g_off), x.data_ptr(), w.data_ptr(),
+                                           out.data_ptr(), _fused._stream(dev))
+    return {name: (out[C * rows * g_off[l]:C * rows * g_off[l + 1]].view(C, T, N, g_off[l + 1] - g_off[l]), names)
+            for l, name in enumerate(levels)}
+
+
+def aggregate_forecasts(levels, yhat, n_samples: int, batch: int, y_true=None, scale=None, quantiles=None,
+                        verify=None, dyn=None, season: Optional[Season] = None, joint: Optional[Joint] = None
+                        ) -> Dict[str, Forecast]:
+    """What ``VAE.forecast(aggregate=levels)`` adds: per level the ``Forecast`` of the aggregated ensemble.
+    ``y_hat`` and the targets are aggregated with the scaler, ``dyn = (dyn, names)`` without, one call each for
+    all levels; then every level's block goes through ``ensemble_summary`` (``quantiles``, ``verify``),
+    ``dynamics_summary``, ``ensemble_season`` (``season`` with the level's ``baseline``, or without an onset) and
+    ``ensemble_joint`` as the baseline did, with ``scale=None``."""
+    levels = check_levels("forecast", levels, int(yhat.shape[-1]))
+    yh = ensemble_aggregate(yhat, levels, scale)
+    yt = ensemble_aggregate(y_true.to(yhat.device), levels, scale) if y_true is not None else None
+    dy = aggregate_dynamics(dyn[0], dyn[1], levels) if dyn is not None else None
+    out = {}
+    for name, lv in levels.items():
+        y_l = None if yt is None else yt[name]
+        fc = ensemble_summary(yh[name], n_samples, batch, y_true=y_l, quantiles=quantiles, verify=verify)
+        if dy is not None:
+            fc.dynamics = dynamics_summary(dy[name][0], dy[name][1], n_samples, batch, quantiles=quantiles)
+        if season is not None:
+            s_l = Season(lv.baseline, season.start, season.every, season.run, season.window)
+            fc.season = ensemble_season(yh[name], n_samples, batch, s_l, y_true=y_l, quantiles=quantiles)
+        if joint is not None:
+            fc.joint = ensemble_joint(yh[name], n_samples, batch, y_l, joint)
+        out[name] = fc
+    return out
 
 
 GRID_SNAP_ULPS = 8

@@ -508,6 +508,50 @@ int ude_forecast_joint(int32_t T, int32_t S, int32_t B, int32_t R, int32_t start
                        double* e_series, double* e_field, double* v_series, double* v_field, double* means,
                        ude_stream_t stream);
 
+/* ude_forecast_aggregate: weighted sums over the regions of an ensemble forecast, row by row (no model) -- the
+ * HHS regions and the nation of the state model as coherent ensembles, S whole trajectories per window.  A level
+ * is a weight matrix (G_l, R), fp64, any sign, rows need not sum to 1; a hierarchy is an ordered list of levels
+ * whose rows are stacked in that order into w (G_tot, R); g_off[l] is level l's first stacked row, g_off[0] = 0
+ * and g_off[n_levels] = G_tot (g_off is a HOST array of n_levels + 1 entries, read before the call returns).
+ * For a row rho of R consecutive fp32 values x[rho, :] and a stacked row g, in fp64:
+ *   v_r = (double)x[rho, r] * scale[r]             (scale null: v_r = (double)x[rho, r])
+ *   acc = 0;  for r = 0 .. R-1 ascending:  acc = acc + w[g, r] * v_r
+ * Every product and every sum is rounded on its own: no fused multiply-add (the library is built with
+ * -ffp-contract=off, which this relies on), r ascending, no reassociation.  The sum is stored as (float)acc, one
+ * round-to-nearest.  A row is a (t, n) of y_hat (T, N, R) (rows = T N) or a (b, t) of y_true (B, T, R) (rows =
+ * B T).  Level l's output is the contiguous block (rows, G_l) at float offset rows * g_off[l] of out (rows *
+ * G_tot floats in all): each block is by itself a (T, N, G_l) array (targets: (B, T, G_l)) that
+ * ude_forecast_summary / _verify / _season / _joint read unchanged, with scale = NULL (it is applied here).  The
+ * aggregated ensemble is thus DEFINED as that fp32 array; everything downstream is the existing definitions on it.
+ * Each element of x is read exactly once, for all levels together.  No workspace, no atomics: the same bits run
+ * to run.  1 <= R <= 4096, 1 <= G_tot <= 256, 1 <= n_levels <= 16, g_off strictly increasing from 0, rows >= 0
+ * (rows = 0: success without a launch), element offsets are 64-bit, no null pointer but scale; UDE_E_INVALID
+ * otherwise, before any launch.  The reference has no counterpart (it trains one model per level): this replaces
+ * a host copy of the whole prediction, or torch glue that rounds and sums in an order nobody has stated. */
+int ude_forecast_aggregate(int64_t rows, int32_t R, int32_t n_levels, const int32_t* g_off, const float* x,
+                           const double* scale, const double* w, float* out, ude_stream_t stream);
+
+/* ude_forecast_aggregate_dyn: the same levels on the dynamics dyn (C, rows, R) fp32 of ude_rk4_forecast_dyn, C =
+ * UDE_DYN_CHANNELS(kind) in its channel order (s, i, r; beta, gamma, r_eff with a rate net; fa_s, fa_i, fa_r with
+ * an augmentation net); UDE_KIND_BAYES in kind is accepted and ignored (the latent fallback emits the same
+ * channels).  No scale.  Per row and stacked row g, with ude_forecast_aggregate's summation rule (fp64, r
+ * ascending, every operation rounded on its own; x_r the fp32 inputs converted to fp64):
+ *   s_g = sum w s_r      i_g = sum w i_r      r_g = sum w r_r      fa_*_g = sum w fa_*_r
+ *   inc_g = sum w[g, r] * ((beta_r * s_r) * i_r)        rec_g = sum w[g, r] * (gamma_r * i_r)
+ *   beta_g = inc_g / (s_g * i_g)      gamma_g = rec_g / i_g      r_eff_g = inc_g / rec_g
+ * from the fp64 sums; each output channel is rounded once to fp32.  inc and rec are the aggregate's new
+ * infections and recoveries per unit time, r_eff_g their ratio, and beta_g / gamma_g the rates a single SIR
+ * population with the aggregate's S and I would need to reproduce them, so r_eff_g = beta_g s_g / gamma_g by
+ * construction (the mean of the regional r_eff is not the aggregate's reproduction number).  Under a scenario
+ * the emitted beta and gamma are already the scaled ones.  Divisions are plain IEEE: i_g = 0 gives inf or NaN, as
+ * the regional r_eff has no clamp either.  The input r_eff channel is not read; every other element is read
+ * once when G_tot <= 64 (the rate planes ceil(G_tot / 64) times beyond).  Level l's output is the block (C,
+ * rows, G_l) at float offset C * rows * g_off[l] of out, same channel order: (C*T, N, G_l) is what
+ * ude_forecast_summary reads.  Limits and errors as ude_forecast_aggregate, and kind without the Bayes bit must
+ * be UDE_KIND_FP, _FA or _FAFP.  Replaces a host copy of the (C, T, N, R) dynamics. */
+int ude_forecast_aggregate_dyn(int32_t kind, int64_t rows, int32_t R, int32_t n_levels, const int32_t* g_off,
+                               const float* dyn, const double* w, float* out, ude_stream_t stream);
+
 /* Library build tag (for logs / tests). */
 const char* ude_build_info(void);
 

@@ -46,12 +46,24 @@ taking turns per grid:
   (b) torch on the device: the torch fp64 definitions of the CPU route on the same device tensor;
   (c) host: a device-to-host copy of y_hat, then the torch fp64 definitions on the host.
 
+``--aggregate`` times the aggregation to 10 groups and the nation (shares of a seeded population; G_tot = 11) of
+one y_hat (57, 8192, 49) and one 9-channel dyn (9, 57, 8192, 49) resident on the device, three routes taking
+turns, each for the prediction and for the dynamics:
+
+  (a) device: ude_amd.forecast.ensemble_aggregate / aggregate_dynamics -- one native call each (its own event
+      time under ``native_calls_ms``), the results left on the device;
+  (b) torch on the device: fp64 ``einsum`` on the same device tensors (another order of operations: it agrees to
+      rounding, not to the bit);
+  (c) host: a device-to-host copy, then NumPy fp64 ``einsum``.
+
+and ``model.forecast(..., aggregate=levels)`` against the same call without it.
+
 Per path: min / median / max of the wall clock, the span between a device event recorded before the
 call and one after its last device operation, and the sum of the gfx950 C-ABI calls' own event times
 (ude_amd.fused.EVENTS).  Prints one JSON line.
 
     python tools/forecast_timing.py [--runs 10] [--warmup 5] [--batch 64] [--samples 128]
-                                    [--dynamics | --season | --scenario | --joint]
+                                    [--dynamics | --season | --scenario | --joint | --aggregate]
 """
 import argparse
 import importlib
@@ -110,6 +122,13 @@ def timed_alternating(fns, runs, warmup):
              "native_calls_ms": {kind: stats([k[kind] for k in kern]) for kind in kern[0]}} for wall, span, kern in acc]
 
 
+def _draw(model, x, S, B, R):
+    """One draw z (S * B, R, L) of the forecast, as VAE.forecast forms it."""
+    mean, std = model.enc(x)
+    eps = torch.randn(S, B, R, model.ld_enc, device="cuda")
+    return (models.reparam(eps, std, mean, S, B, uncertainty=True) + 1e-5).contiguous()
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--runs", type=int, default=10)
@@ -120,6 +139,7 @@ def main():
     ap.add_argument("--season", action="store_true", help="time the seasonal targets instead (see the docstring)")
     ap.add_argument("--scenario", action="store_true", help="time the scenario solve instead (see the docstring)")
     ap.add_argument("--joint", action="store_true", help="time the joint scores instead (see the docstring)")
+    ap.add_argument("--aggregate", action="store_true", help="time the aggregation instead (see the docstring)")
     a = ap.parse_args()
     R, B, S, window = 49, a.batch, a.samples, 8
     torch.manual_seed(0)
@@ -224,6 +244,76 @@ def main():
                           "scores_rel_diff_device_vs_host": agree, "histograms_equal": same_hist,
                           "host_route": res_a, "device_route": res_b,
                           "speedup_min_wall": res_a["wall_ms"]["min"] / res_b["wall_ms"]["min"]}))
+        return
+
+    if a.aggregate:
+        from ude_amd import decoder_head
+        from ude_amd import forecast as fcast
+        T = len(t)
+        rng = np.random.default_rng(3)
+        share = rng.uniform(0.5, 40.0, size=R)
+        member = rng.permutation(np.arange(R) % 10)
+        levels = {"hhs": fcast.Aggregate.from_groups(R, [np.flatnonzero(member == g).tolist() for g in range(10)], share),
+                  "nation": fcast.Aggregate.from_groups(R, [range(R)], share)}
+        G = sum(lv.n_groups for lv in levels.values())
+        with torch.no_grad():
+            res = fcast.solve_decode_dynamics(model.ode, _draw(model, x, S, B, R), t, t[1] - t[0],
+                                              decoder_head.decoder_linear(model.dec))
+        yhat, dyn, names = res
+        model.ode.clear_tracking()
+        C = len(names)
+        w = torch.from_numpy(np.concatenate([lv.weights for lv in levels.values()])).cuda()
+        sc = torch.as_tensor(scaler, dtype=torch.float64).cuda()
+        state = [c for c, n in enumerate(names) if n not in fcast.DYN_RATES]
+
+        def done(e1, out):
+            if e1 is not None:
+                e1.record()
+            return out
+
+        def einsum_dyn(xp, d, wt):
+            """the definitions with einsum in place of the ordered loop (fp64; xp: torch or numpy)"""
+            v = d.astype(np.float64) if xp is np else d.to(torch.float64)
+            out = {c: xp.einsum("gr,tnr->tng", wt, v[c]) for c in state}
+            inc = xp.einsum("gr,tnr->tng", wt, v[3] * v[0] * v[1])
+            rec = xp.einsum("gr,tnr->tng", wt, v[4] * v[1])
+            out[3], out[4], out[5] = inc / (out[0] * out[1]), rec / out[1], inc / rec
+            return xp.stack([out[c] for c in range(C)])
+
+        routes = {
+            "device_yhat": lambda e1=None: done(e1, fcast.ensemble_aggregate(yhat, levels, scale=scaler)),
+            "torch_on_device_yhat": lambda e1=None: done(
+                e1, torch.einsum("gr,tnr->tng", w, yhat.to(torch.float64) * sc).float()),
+            "host_yhat": lambda e1=None: np.einsum(
+                "gr,tnr->tng", w_host, done(e1, yhat.cpu()).numpy().astype(np.float64) * scaler).astype(np.float32),
+            "device_dyn": lambda e1=None: done(e1, fcast.aggregate_dynamics(dyn, names, levels)),
+            "torch_on_device_dyn": lambda e1=None: done(e1, einsum_dyn(torch, dyn, w).float()),
+            "host_dyn": lambda e1=None: einsum_dyn(np, done(e1, dyn.cpu()).numpy(), w_host).astype(np.float32),
+        }
+        w_host = w.cpu().numpy()
+        got = torch.cat(list(routes["device_yhat"]().values()), -1)
+        ref = routes["torch_on_device_yhat"]()
+        got_d = torch.cat([v[0] for v in routes["device_dyn"]().values()], -1)
+        ref_d = routes["torch_on_device_dyn"]()
+        rel = lambda u, v: float(torch.linalg.vector_norm((u - v).double()) / torch.linalg.vector_norm(v.double()))
+        res = timed_alternating(list(routes.values()), a.runs, a.warmup)
+        opts = dict(dynamics=True, quantiles=[0.025, 0.5, 0.975])
+        fc_res = timed_alternating([fused_with(**opts), fused_with(aggregate=levels, **opts)], a.runs, a.warmup)
+        n_in, n_dyn = T * S * B * R * 4, (C - 1) * T * S * B * R * 4
+        n_out, n_dyn_out = T * S * B * G * 4, C * T * S * B * G * 4
+        ev = res[0]["native_calls_ms"]["forecast_aggregate"]["min"]
+        ev_d = res[3]["native_calls_ms"]["forecast_aggregate_dyn"]["min"]
+        print(json.dumps({"tool": "forecast_timing --aggregate", "commit": commit_of(),
+                          "device": torch.cuda.get_device_name(0),
+                          "shape": {"R": R, "S": S, "B": B, "N": S * B, "T": T, "C": C, "levels": [10, 1], "G_tot": G},
+                          "yhat_bytes_read": n_in, "yhat_bytes_written": n_out,
+                          "dyn_bytes_read": n_dyn, "dyn_bytes_written": n_dyn_out,
+                          "fp64_operations": {"yhat": 2 * R * G * T * S * B, "dyn": 2 * R * G * T * S * B * (C - 1)},
+                          "rel_diff_device_vs_einsum": {"yhat": rel(got, ref), "dyn": rel(got_d, ref_d)},
+                          "achieved_bytes_per_s": {"forecast_aggregate": (n_in + n_out) / (ev * 1e-3),
+                                                   "forecast_aggregate_dyn": (n_dyn + n_dyn_out) / (ev_d * 1e-3)},
+                          **dict(zip(routes, res)),
+                          "forecast_dynamics_quantiles": fc_res[0], "forecast_dynamics_quantiles_aggregate": fc_res[1]}))
         return
 
     if a.joint:
