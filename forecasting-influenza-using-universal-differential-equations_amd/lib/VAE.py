@@ -24,6 +24,10 @@ Bayesian RHS (models_bayes.py, run_ode.py's ``*b`` models) takes the same epilog
 the epilogue does not apply (output times between grid points, a non-reference decoder) the latent
 is written and the fused loss head (ude_amd/loss_head.py: decoder + nll_loss + latent_init_loss in
 one kernel pass each) serves the same terms.
+``losses["crps"] = w > 0`` (not in the reference) adds w x the sample-based CRPS of the ensemble right after
+``nll`` -- the score ``forecast(verify=True)`` reports, as a training loss (``train_functions.crps_loss``; on
+a HIP device the gfx950 CRPS head, ude_amd/decoder_head.py ``crps_head``); ``losses["crps_fair"]`` takes the
+fair score.  Absent or 0, nothing changes.
 ``VAE.forecast`` is the forecast side (``evaluate``, ``train(validate=...)``, lib/utils.py ``test``
 on a HIP device): the inference solve with the decoder epilogue and the ensemble summary kernels
 (ude_amd/forecast.py) -- no latent, no checkpoint, only the summary copied to the host.
@@ -423,8 +427,25 @@ class VAE:
                 raise ValueError(f"Expected parameters loc / scale of distribution Normal ({what}) to satisfy the "
                                  "constraints Real() / GreaterThan(lower_bound=0.0), but found invalid values")
 
+    def _crps_term(self, y_pred, y_true, fair):
+        """crps_loss(y_pred, y_true) for the ``crps`` term: on a HIP device the gfx950 CRPS head
+        (ude_amd/decoder_head.py crps_head) over the decoder epilogue's y_hat when y_pred is that
+        prediction, else over y_pred laid out as y_hat; the torch definition on the CPU, for more than
+        1024 samples or another dtype than fp32."""
+        B, S, T, R = y_pred.shape
+        if not y_pred.is_cuda or y_pred.dtype != torch.float32 or S > decoder_head.MAX_CRPS_SAMPLES:
+            return train_functions.crps_loss(y_pred, y_true, fair=fair)
+        src = getattr(self, "_pred_src", None)
+        if src is not None and src[0] is y_pred and src[3] is not None:
+            yhat = src[3]
+        else:
+            yhat = y_pred.permute(2, 1, 0, 3).reshape(T, S * B, R)
+        return decoder_head.crps_head(yhat, y_true, S, B, fair=fair)
+
     def calc_loss(self, y_pred, y_true, losses):
-        """The reference's loss composition (:142-198).  In a data-parallel step
+        """The reference's loss composition (:142-198), plus the optional ``crps`` term (``losses["crps"]``
+        = its weight, ``losses["crps_fair"]`` the fair score: train_functions.crps_loss, added after
+        ``nll``; absent or 0: nothing changes).  In a data-parallel step
         (``self._dp_w``) each term is weighted by this rank's share of the global loss -- batch
         means by the window fraction, sums by 1, terms of the (already global) side statistics and
         of the parameters by 1/world -- and the reported values are the all-reduced global ones."""
@@ -446,6 +467,8 @@ class VAE:
         if losses.get("nll", True):
             terms["nll"] = fused[0] if (fused is not None and fused[0] is not None) \
                 else train_functions.nll_loss(y_pred, y_true)
+        if losses.get("crps", 0) > 0:
+            terms["crps"] = losses["crps"] * self._crps_term(y_pred, y_true, bool(losses.get("crps_fair", False)))
         if losses.get("kl_z", True):
             prior = models.make_prior(self.mean, latent_dim=self.ld_ode, device=self.device)
             kl = train_functions.kl_divergence(prior, Normal(self.mean, self.std)).sum(-1).mean()
@@ -469,7 +492,7 @@ class VAE:
         self._validate_normals(checks)
         if dpw is not None:
             frac, glob = dpw
-            kind = {"mse": frac, "nll": frac, "kl_latent": frac, "reg_loss": 1.0}
+            kind = {"mse": frac, "nll": frac, "crps": frac, "kl_latent": frac, "reg_loss": 1.0}
             terms = {k: v * kind.get(k, glob) for k, v in terms.items()}
         loss = torch.tensor(0.0, requires_grad=True)
         for v in terms.values():
@@ -577,13 +600,22 @@ class VAE:
             if sched is not None:
                 sched.step()
             self._history.reset()
+            # with the CRPS term on, the history also gets the ensemble's own CRPS (forecast(verify=True).crps)
+            with_crps = losses.get("crps", 0) > 0
             if validate is not None and _on_hip(self):
-                nll = self.forecast(validate["x_test"], validate["t"], n_samples=validate["n_samples"],
-                                    y_true=validate["y_test"], scaler=validate["scaler"]).nll.cpu().numpy()
+                fc = self.forecast(validate["x_test"], validate["t"], n_samples=validate["n_samples"],
+                                   y_true=validate["y_test"], scaler=validate["scaler"],
+                                   verify=True if with_crps else None)
+                nll = fc.nll.cpu().numpy()
                 # the reference scores range(len(t)) with the TRAINING grid t (ref lib/VAE.py:278)
                 nlls = [nll[g] for g in range(len(t))]
                 self._history.epoch_history[-1]["forecast_nll"] = np.mean(nlls[-28:])
                 self._history.epoch_history[-1]["all_nll"] = np.mean(nlls)
+                if with_crps:
+                    crps = fc.crps.cpu().numpy()
+                    crpss = [crps[g] for g in range(len(t))]
+                    self._history.epoch_history[-1]["forecast_crps"] = np.mean(crpss[-28:])
+                    self._history.epoch_history[-1]["all_crps"] = np.mean(crpss)
             elif validate is not None:
                 y_pred = self(validate["x_test"], validate["t"], n_samples=validate["n_samples"], training=False)
                 y_pr, y_te = _scale_forecast(y_pred, validate["y_test"], validate["scaler"])
@@ -592,6 +624,16 @@ class VAE:
                 nlls = [Metrics.nll(y_te[:, g, :], mu[:, g, :], sd[:, g, :]) for g in range(len(t))]
                 self._history.epoch_history[-1]["forecast_nll"] = np.mean(nlls[-28:])
                 self._history.epoch_history[-1]["all_nll"] = np.mean(nlls)
+                if with_crps:
+                    # forecast(verify=True).crps of this prediction (the CPU route of forecast summarises
+                    # __call__'s y_pred the same way)
+                    B_v, S_v, T_v, R_v = y_pred.shape
+                    yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(T_v, S_v * B_v, R_v)
+                    crps = ude_forecast.ensemble_summary(yhat, S_v, B_v, y_true=validate["y_test"],
+                                                         scale=validate["scaler"], verify=True).crps.cpu().numpy()
+                    crpss = [crps[g] for g in range(len(t))]
+                    self._history.epoch_history[-1]["forecast_crps"] = np.mean(crpss[-28:])
+                    self._history.epoch_history[-1]["all_crps"] = np.mean(crpss)
             if disable:
                 print(epoch + 1, end=" ")
                 print_rounded_dict(self._history.epoch_history[-1], decimals=3)

@@ -1,7 +1,8 @@
 """Drop-in for lib/train_functions.py: the loss helpers lib/VAE.py composes around
 the ODE solve (KL_annealing :17-44, get_kl_params :77-80, nll_loss :81-90,
 make_prior / reparam :92-102, latent_init_loss :116-126, history :142-176,
-kl_div :178-179, make_file :12-15) with the reference's signatures."""
+kl_div :178-179, make_file :12-15) with the reference's signatures.  ``crps_loss`` is not in the reference:
+the sample-based CRPS of the MC samples as a training loss, next to ``nll_loss``."""
 import os
 import subprocess
 
@@ -53,6 +54,47 @@ def nll_loss(y_pred, y, mean=True):
     """Gaussian NLL of y under the MC-sample mean/std (dim 1); entries with y == -1 are masked."""
     dist = Normal(torch.mean(y_pred, 1), torch.std(y_pred, 1))
     out = -dist.log_prob(y) * (y != -1).float()
+    return out.mean() if mean else out
+
+
+class _SortedCrps(torch.autograd.Function):
+    """Per-group CRPS of the samples along dim 1 (the definition at ude_crps_forward in include/ude_rk4.h):
+    forward from the sorted samples, backward the mid-rank subgradient num_s / (S D) from two searches of
+    every sample in its sorted group.  Plain autograd through ``sort`` would break ties by index."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y, D):
+        S = y_pred.shape[1]
+        xs = y_pred.sort(dim=1).values
+        rank = (torch.arange(S, dtype=y_pred.dtype, device=y_pred.device) * 2 - (S - 1)).view(1, S, 1, 1)
+        live = y != -1
+        c = (y_pred - y.unsqueeze(1)).abs().sum(1) / S - (rank * xs).sum(1) / (S * D)
+        ctx.save_for_backward(y_pred, xs, y, live)
+        ctx.D = D
+        return c * live.to(c.dtype)
+
+    @staticmethod
+    def backward(ctx, g):
+        y_pred, xs, y, live = ctx.saved_tensors
+        S, D = y_pred.shape[1], ctx.D
+        cols = xs.movedim(1, -1).contiguous()                   # (B, T, R, S): searchsorted's innermost dim
+        v = y_pred.movedim(1, -1).contiguous()
+        n_lt = torch.searchsorted(cols, v, right=False)
+        n_le = torch.searchsorted(cols, v, right=True)
+        num = D * torch.sign(v - y.unsqueeze(-1)).to(torch.int64) - (n_lt + n_le - S)
+        num = num * live.unsqueeze(-1)
+        return (g.unsqueeze(-1) * num.to(g.dtype) / (S * D)).movedim(-1, 1), None, None
+
+
+def crps_loss(y_pred, y, fair=False, mean=True):
+    """Sample-based CRPS of the MC samples (dim 1 of y_pred (B, S, T, R)) against y (B, T, R): per group
+    E|X - y| - sum_ij |x_i - x_j| / (2 S D), D = S, or S - 1 with ``fair``; entries with y == -1 are
+    masked and count in the mean's divisor, as in ``nll_loss``.  With D = S it is the ``crps`` that
+    ``forecast(verify=True)`` reports.  O(S log S) per group; the gradient is the symmetric (mid-rank) one."""
+    S = y_pred.shape[1]
+    if fair and S < 2:
+        raise ValueError("crps_loss: the fair score needs at least 2 samples")
+    out = _SortedCrps.apply(y_pred, y.to(y_pred.dtype), S - 1 if fair else S)
     return out.mean() if mean else out
 
 

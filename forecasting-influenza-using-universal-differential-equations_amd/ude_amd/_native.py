@@ -150,6 +150,9 @@ _CABI: Dict[str, tuple] = {
     "ude_nll_workspace": _sig(None, _pd, (3, _i32), _pi64),
     "ude_nll_forward": _sig("nll_forward", _pd, (3, _i32), (5, _vp)),
     "ude_nll_backward": _sig("nll_backward", _pd, (3, _i32), (6, _vp)),
+    "ude_crps_workspace": _sig(None, (4, _i32), _pi64),
+    "ude_crps_forward": _sig("crps_forward", (5, _i32), (5, _vp)),
+    "ude_crps_backward": _sig("crps_backward", (5, _i32), (4, _vp)),
     "ude_rhs_eval_vjp": _sig("rhs_eval_vjp", _pd, _pp, (4, _vp), _f32, (4, _vp)),
     "ude_lincomb": _sig(None, _i64, _vp, _pvp, _i32, (3, _vp)),
     "ude_scaled_sumsq": _sig("scaled_sumsq", _i64, (3, _vp), (2, _f64), (2, _vp)),
@@ -256,6 +259,9 @@ class NativeLib:
 
     def nll_workspace(self, desc, T, S, B) -> int:
         return self._workspace("ude_nll_workspace", desc, T, S, B)
+
+    def crps_workspace(self, T, S, B, R) -> int:
+        return self._workspace("ude_crps_workspace", T, S, B, R)
 
     def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
         return self._workspace("ude_forecast_summary_workspace", T, S, B, R, n_q)

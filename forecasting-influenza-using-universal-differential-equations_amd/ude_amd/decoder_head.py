@@ -13,6 +13,10 @@ path (``FusedRK4Dec``, ude_rk4_forward_dec): ``y_hat (T, N, R)`` and the reg sum
 something reads it (``LazyLatent``).  ``nll_head`` is ``nll_loss(y_pred, y)``
 (lib/train_functions.py:81-90) over ``y_hat`` on the gfx950 nll kernels (per (t, b, r)
 sample mean / unbiased std, -log N(y), masked y == -1, mean), forward and backward one pass each.
+``crps_head`` is ``crps_loss(y_pred, y)`` (lib/train_functions.py; not in the reference: the sample-based
+CRPS of the ensemble as a training loss) over the same ``y_hat`` on the gfx950 CRPS kernels
+(csrc/ude_crps.h: the summary kernel's sorted tile, the mid-rank gradient's integer numerators kept for a
+one-pass backward).
 """
 from __future__ import annotations
 
@@ -115,6 +119,65 @@ class _NllHead(torch.autograd.Function):
             lib.nll_backward(desc, T, S, B, yhat.data_ptr(), y.data_ptr(), grad.data_ptr(), ws.data_ptr(),
                              dyhat.data_ptr(), _fused._stream(dev))
         return None, None, None, None, None, dyhat, None
+
+
+MAX_CRPS_SAMPLES = 1024   # FC_MAX_SQ of csrc/ude_forecast.h: the largest S the kernel's sorted tile holds
+
+
+class _CrpsHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lib, T, S, B, R, fair, yhat, y):
+        dev = yhat.device
+        # every byte of it: 2 bytes per element of y_hat behind the partials, not always a multiple of 4
+        ws = torch.empty(lib.crps_workspace(T, S, B, R), dtype=torch.uint8, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        yhat, y = yhat.contiguous(), y.contiguous()
+        with _fused._timed("crps_fwd"):
+            lib.crps_forward(T, S, B, R, fair, yhat.data_ptr(), y.data_ptr(), ws.data_ptr(), out.data_ptr(),
+                             _fused._stream(dev))
+        ctx.meta = (lib, T, S, B, R, fair)
+        ctx.save_for_backward(ws)                 # the backward reads the workspace's numerators only
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib, T, S, B, R, fair = ctx.meta
+        ws, = ctx.saved_tensors
+        dev = ws.device
+        grad = g.reshape(1).float().contiguous()
+        dyhat = torch.empty((T, S * B, R), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), _fused._timed("crps_bwd"):
+            lib.crps_backward(T, S, B, R, fair, grad.data_ptr(), ws.data_ptr(), dyhat.data_ptr(), _fused._stream(dev))
+        return None, None, None, None, None, None, dyhat, None
+
+
+def crps_head(yhat: torch.Tensor, y: torch.Tensor, n_samples: int, batch: int, fair: bool = False):
+    """``train_functions.crps_loss`` (the definition at ude_crps_forward in include/ude_rk4.h) of y_pred =
+    y_hat (T, S*B, R) as lib/VAE.py:138 reshapes it, against targets y (B, T, R): a scalar that carries
+    autograd to ``yhat`` -- the decoder epilogue's output or any other fp32 HIP tensor of that shape.  On
+    the gfx950 CRPS kernels (no model: any library); more than 1024 samples take the torch definition on
+    the device."""
+    from . import forecast as _forecast
+    import lib.train_functions as train_functions
+    if yhat.dim() != 3:
+        raise ValueError(f"crps_head: y_hat {tuple(yhat.shape)} is not (T, S*B, R)")
+    T, N, R = (int(v) for v in yhat.shape)
+    S, B = int(n_samples), int(batch)
+    if N != S * B or tuple(y.shape) != (B, T, R) or S < 1:
+        raise ValueError(f"crps_head: y_hat {tuple(yhat.shape)} / targets {tuple(y.shape)} do not match "
+                         f"S={n_samples}, B={batch}")
+    if fair and S < 2:
+        raise ValueError("crps_head: the fair score needs at least 2 samples")
+    if not yhat.is_cuda or yhat.dtype != torch.float32:
+        raise ValueError("crps_head: y_hat is an fp32 tensor on a HIP device (train_functions.crps_loss "
+                         "is the definition for any other)")
+    if S > MAX_CRPS_SAMPLES:
+        return train_functions.crps_loss(yhat.reshape(T, S, B, R).permute(2, 1, 0, 3), y.to(torch.float32), fair=fair)
+    lib = _forecast._library()
+    if lib is None:
+        raise _native.UdeError("crps_head: no gfx950 library is built (run __graft_entry__.build())")
+    with torch.cuda.device(yhat.device):
+        return _CrpsHead.apply(lib, T, S, B, R, int(bool(fair)), yhat, y.to(device=yhat.device, dtype=torch.float32))
 
 
 def nll_head(ode, yhat: torch.Tensor, y: torch.Tensor, n_samples: int, batch: int):

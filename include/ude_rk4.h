@@ -322,6 +322,39 @@ int ude_nll_forward(const UdeModelDesc* m, int32_t T, int32_t S, int32_t B, cons
 int ude_nll_backward(const UdeModelDesc* m, int32_t T, int32_t S, int32_t B, const float* yhat, const float* y,
                      const float* grad, const void* ws, float* dyhat, ude_stream_t stream);
 
+/* ude_crps_*: the CRPS training head -- the sample-based continuous ranked probability score of the ensemble
+ * y_hat (T, S*B, R) fp32 (sample n = s*B + b; no model, any y_hat: the decoder epilogue's or another) against
+ * targets y (B, T, R) fp32, as a differentiable loss.  y == -1 means missing, as in nll_loss.  This is the one
+ * definition the kernels (csrc/ude_crps.h), lib/train_functions.py crps_loss and the tests share.
+ *   Per group (t, b, r): the samples x_s = y_hat[t, s*B+b, r], sorted x_(0) <= .. <= x_(S-1), the target
+ *   y = y[b, t, r], D = S, or D = S - 1 with fair (the unbiased "fair" score of a small ensemble),
+ *     c = (1 / S) sum_s |x_s - y| - (1 / (S D)) sum_i (2 i - S + 1) x_(i)
+ *       = E|X - y| - sum_i sum_j |x_i - x_j| / (2 S D); with D = S exactly ude_forecast_verify's crps.
+ *   loss = (1 / (B T R)) sum over the groups of c [y != -1]: nll_loss's mask and divisor (a masked group
+ *   counts in the divisor).
+ *   Gradient, the symmetric (mid-rank) subgradient -- what autograd gives on the pairwise form, ties included:
+ *     d loss / d x_s = (g / (B T R)) num_s / (S D),   num_s = D sgn(x_s - y) - (n_lt + n_le - S),
+ *     n_lt = #{j: x_j < x_s}, n_le = #{j: x_j <= x_s} (counts x_s itself), sgn(0) = 0, num_s = 0 for a masked
+ *     group.  num_s is formed as an integer, so an exact zero stays exact.
+ *   Arithmetic: everything after the fp32 load is fp64; out[0] and d y_hat are fp32, each rounded once from
+ *   fp64: d y_hat[e] = (float)((double)grad[0] / (B T R) * num[e] / (S D)).  No scaler: training targets are in
+ *   model units.  Fixed-order sums, no atomics: the same bits run to run.
+ * ude_crps_forward writes out[0] = loss and keeps in ws (ude_crps_workspace() bytes: the per-workgroup fp64
+ * partials and the int16 numerators, 2 bytes per element of y_hat) what ude_crps_backward needs: given grad
+ * (device float, d loss / d crps) it writes d y_hat in one streaming pass (it reads neither y_hat nor y and does
+ * not sort).  Stream-ordered, caller-owned buffers, no host read.  ws must be 8-byte aligned (the fp64 partials
+ * are at its start) and hold all ude_crps_workspace() bytes, which need not be a multiple of 4; the backward
+ * uses 16-byte accesses when ws and dyhat are both 16-byte aligned and scalar ones otherwise.  1 <= S <= 1024,
+ * S >= 2 with fair, T <= 65535, no null pointer; UDE_E_INVALID otherwise, before any launch.  S = 1 without fair is the masked MAE.  The
+ * reference has no counterpart: it trains on nll_loss of the sample mean / std alone. */
+int ude_crps_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int64_t* ws_bytes);
+
+int ude_crps_forward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, const float* yhat, const float* y,
+                     void* ws, float* out, ude_stream_t stream);
+
+int ude_crps_backward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, const float* grad, const void* ws,
+                      float* dyhat, ude_stream_t stream);
+
 /* ---- odeint_adjoint's augmented dynamics (torchdiffeq adjoint; the solver API lib/VAE.py:5 imports) --
  * One evaluation of the right-hand side and its VJP in ONE launch: f_out = f_scale * f(x) (N, R, L),
  * dx = cot_f^T df/dx (N, R, L) and dparams = cot_f^T df/dtheta (torch parameter order).  The reversed
