@@ -7,6 +7,7 @@
 #include "ude_vec.h"      // model-independent vector kernels (compiled in both passes)
 #include "ude_forecast.h" // model-independent ensemble summary kernels (likewise)
 #include "ude_crps.h"     // model-independent CRPS training head over the summary's tile (likewise)
+#include "ude_energy.h"   // model-independent energy-score training head (likewise)
 #include "ude_season.h"   // model-independent seasonal-target kernels (likewise)
 #include "ude_joint.h"    // model-independent energy / variogram score kernels (likewise)
 #include "ude_aggregate.h" // model-independent aggregation over the regions (likewise)
@@ -301,6 +302,20 @@ int ude_crps_forward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, c
 int ude_crps_backward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, const float* grad, const void* ws,
                       float* dyhat, ude_stream_t stream) {
   return ude::crps_backward(T, S, B, R, fair, grad, ws, dyhat, (hipStream_t)stream);
+}
+
+int ude_energy_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int64_t* ws_bytes) {
+  return ude::energy_workspace(T, S, B, R, block, ws_bytes);
+}
+
+int ude_energy_forward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int32_t fair, const float* yhat,
+                       const float* y, void* ws, float* out, ude_stream_t stream) {
+  return ude::energy_forward(T, S, B, R, block, fair, yhat, y, ws, out, (hipStream_t)stream);
+}
+
+int ude_energy_backward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int32_t fair, const float* yhat,
+                        const float* y, const float* grad, float* dyhat, ude_stream_t stream) {
+  return ude::energy_backward(T, S, B, R, block, fair, yhat, y, grad, dyhat, (hipStream_t)stream);
 }
 
 int ude_rk4_forecast_dec(const UdeModelDesc* m, const UdeProblem* p, const float* pack, const void* sched,

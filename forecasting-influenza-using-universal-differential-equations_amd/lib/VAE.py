@@ -28,6 +28,12 @@ one kernel pass each) serves the same terms.
 ``nll`` -- the score ``forecast(verify=True)`` reports, as a training loss (``train_functions.crps_loss``; on
 a HIP device the gfx950 CRPS head, ude_amd/decoder_head.py ``crps_head``); ``losses["crps_fair"]`` takes the
 fair score.  Absent or 0, nothing changes.
+``losses["energy"] = w > 0`` (not in the reference either) adds w x the energy score of the ensemble's
+trajectories right after ``crps`` -- the joint score ``forecast(joint=True)`` reports, as a training loss
+(``train_functions.energy_loss``; on a HIP device the gfx950 energy head, ``energy_head``);
+``losses["energy_block"]`` chooses what is scored jointly ("joint": all days and regions of a window, "series":
+each region's days, "field": each day's regions), ``losses["energy_fair"]`` the fair score.  Absent or 0,
+nothing changes.
 ``VAE.forecast`` is the forecast side (``evaluate``, ``train(validate=...)``, lib/utils.py ``test``
 on a HIP device): the inference solve with the decoder epilogue and the ensemble summary kernels
 (ude_amd/forecast.py) -- no latent, no checkpoint, only the summary copied to the host.
@@ -442,10 +448,28 @@ class VAE:
             yhat = y_pred.permute(2, 1, 0, 3).reshape(T, S * B, R)
         return decoder_head.crps_head(yhat, y_true, S, B, fair=fair)
 
+    def _energy_term(self, y_pred, y_true, block, fair):
+        """energy_loss(y_pred, y_true) for the ``energy`` term, routed as ``_crps_term`` routes the CRPS: on a
+        HIP device the gfx950 energy head (ude_amd/decoder_head.py energy_head) over the decoder epilogue's
+        y_hat or over y_pred laid out as y_hat; the torch definition on the CPU, beyond the kernels' sizes
+        or for another dtype than fp32."""
+        B, S, T, R = y_pred.shape
+        if not y_pred.is_cuda or y_pred.dtype != torch.float32:
+            return train_functions.energy_loss(y_pred, y_true, block=block, fair=fair)
+        src = getattr(self, "_pred_src", None)
+        if src is not None and src[0] is y_pred and src[3] is not None:
+            yhat = src[3]
+        else:
+            yhat = y_pred.permute(2, 1, 0, 3).reshape(T, S * B, R)
+        return decoder_head.energy_head(yhat, y_true, S, B, block=block, fair=fair)
+
     def calc_loss(self, y_pred, y_true, losses):
         """The reference's loss composition (:142-198), plus the optional ``crps`` term (``losses["crps"]``
         = its weight, ``losses["crps_fair"]`` the fair score: train_functions.crps_loss, added after
-        ``nll``; absent or 0: nothing changes).  In a data-parallel step
+        ``nll``; absent or 0: nothing changes) and the optional ``energy`` term (``losses["energy"]`` = its
+        weight, ``losses["energy_block"]`` = "joint" (default), "series" or "field", ``losses["energy_fair"]``
+        the fair score: train_functions.energy_loss, added after ``crps``; absent or 0: nothing changes).
+        In a data-parallel step
         (``self._dp_w``) each term is weighted by this rank's share of the global loss -- batch
         means by the window fraction, sums by 1, terms of the (already global) side statistics and
         of the parameters by 1/world -- and the reported values are the all-reduced global ones."""
@@ -469,6 +493,13 @@ class VAE:
                 else train_functions.nll_loss(y_pred, y_true)
         if losses.get("crps", 0) > 0:
             terms["crps"] = losses["crps"] * self._crps_term(y_pred, y_true, bool(losses.get("crps_fair", False)))
+        if losses.get("energy", 0) > 0:
+            block = losses.get("energy_block", "joint")
+            if block not in train_functions.ENERGY_BLOCKS:
+                raise ValueError(f"calc_loss: losses['energy_block'] = {block!r} is not one of "
+                                 f"{train_functions.ENERGY_BLOCKS}")
+            terms["energy"] = losses["energy"] * self._energy_term(y_pred, y_true, block,
+                                                                   bool(losses.get("energy_fair", False)))
         if losses.get("kl_z", True):
             prior = models.make_prior(self.mean, latent_dim=self.ld_ode, device=self.device)
             kl = train_functions.kl_divergence(prior, Normal(self.mean, self.std)).sum(-1).mean()
@@ -492,7 +523,7 @@ class VAE:
         self._validate_normals(checks)
         if dpw is not None:
             frac, glob = dpw
-            kind = {"mse": frac, "nll": frac, "crps": frac, "kl_latent": frac, "reg_loss": 1.0}
+            kind = {"mse": frac, "nll": frac, "crps": frac, "energy": frac, "kl_latent": frac, "reg_loss": 1.0}
             terms = {k: v * kind.get(k, glob) for k, v in terms.items()}
         loss = torch.tensor(0.0, requires_grad=True)
         for v in terms.values():
@@ -602,10 +633,12 @@ class VAE:
             self._history.reset()
             # with the CRPS term on, the history also gets the ensemble's own CRPS (forecast(verify=True).crps)
             with_crps = losses.get("crps", 0) > 0
+            # with the energy term on, likewise the joint energy score (forecast(joint=True).joint.energy_joint_mean)
+            with_energy = losses.get("energy", 0) > 0
             if validate is not None and _on_hip(self):
                 fc = self.forecast(validate["x_test"], validate["t"], n_samples=validate["n_samples"],
                                    y_true=validate["y_test"], scaler=validate["scaler"],
-                                   verify=True if with_crps else None)
+                                   verify=True if with_crps else None, joint=True if with_energy else None)
                 nll = fc.nll.cpu().numpy()
                 # the reference scores range(len(t)) with the TRAINING grid t (ref lib/VAE.py:278)
                 nlls = [nll[g] for g in range(len(t))]
@@ -616,6 +649,8 @@ class VAE:
                     crpss = [crps[g] for g in range(len(t))]
                     self._history.epoch_history[-1]["forecast_crps"] = np.mean(crpss[-28:])
                     self._history.epoch_history[-1]["all_crps"] = np.mean(crpss)
+                if with_energy:
+                    self._history.epoch_history[-1]["forecast_energy"] = float(fc.joint.energy_joint_mean.cpu())
             elif validate is not None:
                 y_pred = self(validate["x_test"], validate["t"], n_samples=validate["n_samples"], training=False)
                 y_pr, y_te = _scale_forecast(y_pred, validate["y_test"], validate["scaler"])
@@ -634,6 +669,12 @@ class VAE:
                     crpss = [crps[g] for g in range(len(t))]
                     self._history.epoch_history[-1]["forecast_crps"] = np.mean(crpss[-28:])
                     self._history.epoch_history[-1]["all_crps"] = np.mean(crpss)
+                if with_energy:
+                    # forecast(joint=True).joint of this prediction, as the CPU route of forecast forms it
+                    B_v, S_v, T_v, R_v = y_pred.shape
+                    yhat = y_pred.detach().permute(2, 1, 0, 3).reshape(T_v, S_v * B_v, R_v)
+                    joint = ude_forecast.ensemble_joint(yhat, S_v, B_v, validate["y_test"], scale=validate["scaler"])
+                    self._history.epoch_history[-1]["forecast_energy"] = float(joint.energy_joint_mean.cpu())
             if disable:
                 print(epoch + 1, end=" ")
                 print_rounded_dict(self._history.epoch_history[-1], decimals=3)

@@ -2,13 +2,15 @@
 the ODE solve (KL_annealing :17-44, get_kl_params :77-80, nll_loss :81-90,
 make_prior / reparam :92-102, latent_init_loss :116-126, history :142-176,
 kl_div :178-179, make_file :12-15) with the reference's signatures.  ``crps_loss`` is not in the reference:
-the sample-based CRPS of the MC samples as a training loss, next to ``nll_loss``."""
+the sample-based CRPS of the MC samples as a training loss, next to ``nll_loss``; nor is ``energy_loss``, the
+energy score of the MC trajectories (the joint score, where the CRPS is the marginal one)."""
 import os
 import subprocess
 
 import numpy as np
 import torch
 from torch.distributions import Normal, kl_divergence  # noqa: F401  (re-exported, lib/VAE.py:167)
+from torch.utils.checkpoint import checkpoint
 
 from lib.models import make_prior, reparam  # noqa: F401
 
@@ -96,6 +98,61 @@ def crps_loss(y_pred, y, fair=False, mean=True):
         raise ValueError("crps_loss: the fair score needs at least 2 samples")
     out = _SortedCrps.apply(y_pred, y.to(y_pred.dtype), S - 1 if fair else S)
     return out.mean() if mean else out
+
+
+ENERGY_BLOCKS = ("joint", "series", "field")
+ENERGY_CHUNK_BYTES = 256 << 20      # the largest temporary energy_loss forms, with or without autograd
+
+
+def _guarded_root(s):
+    """sqrt(s) with the value and the gradient 0 at s == 0 (plain sqrt's gradient there is inf, times 0: NaN)."""
+    pos = s > 0
+    return torch.where(pos, torch.sqrt(torch.where(pos, s, torch.ones_like(s))), torch.zeros_like(s))
+
+
+def energy_loss(y_pred, y, block="joint", fair=False):
+    """Energy score of the MC trajectories (dim 1 of y_pred (B, S, T, R)) against y (B, T, R), the definition
+    at ude_energy_forward in include/ude_rk4.h: per window and block C of coordinates -- ``"joint"`` all T R,
+    ``"series"`` region r's T times, ``"field"`` the R regions at time t -- ES_C = sum_i |x_i - y|_C / S -
+    sum_ij |x_i - x_j|_C / (2 S D), D = S, or S - 1 with ``fair``; a coordinate with y == -1 is dropped from its
+    blocks, a block without a live coordinate counts 0 in the mean over the B K blocks.  With D = S it is the
+    mean over the windows of the ``energy_joint`` / ``energy_series`` / ``energy_field`` that
+    ``forecast(joint=True)`` reports.  Pairwise differences are formed directly, windows (and, where one window
+    is too large, samples i) a chunk at a time, so that no temporary exceeds about 256 MB; under autograd each
+    chunk keeps only its inputs and forms its differences again in the backward (``torch.utils.checkpoint``),
+    so that bound holds on the gradient path too.  The guarded root gives a norm of exactly 0 the gradient 0."""
+    if block not in ENERGY_BLOCKS:
+        raise ValueError(f"energy_loss: block {block!r} is not one of {ENERGY_BLOCKS}")
+    B, S, T, R = y_pred.shape
+    if fair and S < 2:
+        raise ValueError("energy_loss: the fair score needs at least 2 samples")
+    D = S - 1 if fair else S
+    K = {"joint": 1, "series": R, "field": T}[block]
+    over = {"joint": (-2, -1), "series": (-2,), "field": (-1,)}[block]    # the dims a block's norm sums over
+    y = y.to(y_pred.dtype)
+    live = (y != -1).to(y_pred.dtype)
+
+    def pair_sum(xi, x, m):
+        """sum over the chunk's pairs and blocks of |x_i - x_j|_C: the (n, ni, S, T, R) temporaries live here"""
+        d2 = torch.square(xi.unsqueeze(2) - x.unsqueeze(1)) * m.unsqueeze(1)
+        return _guarded_root(d2.sum(over)).sum()
+
+    recompute = torch.is_grad_enabled() and y_pred.requires_grad
+    per_window = S * S * T * R * y_pred.element_size()
+    nb = max(1, min(B, ENERGY_CHUNK_BYTES // per_window))
+    total = y_pred.new_zeros(())
+    for b0 in range(0, B, nb):
+        x, yy, m = y_pred[b0:b0 + nb], y[b0:b0 + nb].unsqueeze(1), live[b0:b0 + nb].unsqueeze(1)
+        n = x.shape[0]
+        first = _guarded_root((torch.square(x - yy) * m).sum(over)).sum()
+        ni = max(1, min(S, ENERGY_CHUNK_BYTES // (n * S * T * R * y_pred.element_size())))
+        pairs = y_pred.new_zeros(())
+        for i0 in range(0, S, ni):
+            xi = x[:, i0:i0 + ni]
+            pairs = pairs + (checkpoint(pair_sum, xi, x, m, use_reentrant=False) if recompute
+                             else pair_sum(xi, x, m))
+        total = total + (first / S - pairs / (2.0 * S * D))
+    return total / (B * K)
 
 
 def latent_init_loss(x):

@@ -153,6 +153,9 @@ _CABI: Dict[str, tuple] = {
     "ude_crps_workspace": _sig(None, (4, _i32), _pi64),
     "ude_crps_forward": _sig("crps_forward", (5, _i32), (5, _vp)),
     "ude_crps_backward": _sig("crps_backward", (5, _i32), (4, _vp)),
+    "ude_energy_workspace": _sig(None, (5, _i32), _pi64),
+    "ude_energy_forward": _sig("energy_forward", (6, _i32), (5, _vp)),
+    "ude_energy_backward": _sig("energy_backward", (6, _i32), (5, _vp)),
     "ude_rhs_eval_vjp": _sig("rhs_eval_vjp", _pd, _pp, (4, _vp), _f32, (4, _vp)),
     "ude_lincomb": _sig(None, _i64, _vp, _pvp, _i32, (3, _vp)),
     "ude_scaled_sumsq": _sig("scaled_sumsq", _i64, (3, _vp), (2, _f64), (2, _vp)),
@@ -262,6 +265,13 @@ class NativeLib:
 
     def crps_workspace(self, T, S, B, R) -> int:
         return self._workspace("ude_crps_workspace", T, S, B, R)
+
+    def energy_workspace(self, T, S, B, R, block) -> int:
+        return self._workspace("ude_energy_workspace", T, S, B, R, block)
+
+    def energy_supported(self, T, S, B, R, block) -> bool:
+        """Whether the energy kernels take this shape (the limits live in csrc/ude_energy.h alone)."""
+        return self._rc("ude_energy_workspace", T, S, B, R, block, ctypes.c_int64(0)) == UDE_OK
 
     def forecast_summary_workspace(self, T, S, B, R, n_q) -> int:
         return self._workspace("ude_forecast_summary_workspace", T, S, B, R, n_q)

@@ -17,6 +17,9 @@ sample mean / unbiased std, -log N(y), masked y == -1, mean), forward and backwa
 CRPS of the ensemble as a training loss) over the same ``y_hat`` on the gfx950 CRPS kernels
 (csrc/ude_crps.h: the summary kernel's sorted tile, the mid-rank gradient's integer numerators kept for a
 one-pass backward).
+``energy_head`` is ``energy_loss(y_pred, y)`` (likewise not in the reference: the energy score of the
+ensemble's trajectories, the joint score) over the same ``y_hat`` on the gfx950 energy kernels
+(csrc/ude_energy.h: direct fp64 pair differences per block; the backward forms them again).
 """
 from __future__ import annotations
 
@@ -178,6 +181,74 @@ def crps_head(yhat: torch.Tensor, y: torch.Tensor, n_samples: int, batch: int, f
         raise _native.UdeError("crps_head: no gfx950 library is built (run __graft_entry__.build())")
     with torch.cuda.device(yhat.device):
         return _CrpsHead.apply(lib, T, S, B, R, int(bool(fair)), yhat, y.to(device=yhat.device, dtype=torch.float32))
+
+
+# The block kinds are named once, in lib.train_functions.ENERGY_BLOCKS; the C-ABI's integer is the index there and
+# the header's UDE_ENERGY_JOINT / _SERIES / _FIELD (0 / 1 / 2) -- checked against the header by the tests.
+
+
+class _EnergyHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, lib, T, S, B, R, kind, fair, yhat, y):
+        dev = yhat.device
+        ws = torch.empty(lib.energy_workspace(T, S, B, R, kind) // 8, dtype=torch.float64, device=dev)
+        out = torch.empty(1, dtype=torch.float32, device=dev)
+        yhat, y = yhat.contiguous(), y.contiguous()
+        with _fused._timed("energy_fwd"):
+            lib.energy_forward(T, S, B, R, kind, fair, yhat.data_ptr(), y.data_ptr(), ws.data_ptr(), out.data_ptr(),
+                               _fused._stream(dev))
+        ctx.meta = (lib, T, S, B, R, kind, fair)
+        ctx.save_for_backward(yhat, y)            # the backward forms the pair distances again: no workspace kept
+        return out[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        lib, T, S, B, R, kind, fair = ctx.meta
+        yhat, y = ctx.saved_tensors
+        dev = yhat.device
+        grad = g.reshape(1).float().contiguous()
+        dyhat = torch.empty((T, S * B, R), dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev), _fused._timed("energy_bwd"):
+            lib.energy_backward(T, S, B, R, kind, fair, yhat.data_ptr(), y.data_ptr(), grad.data_ptr(),
+                                dyhat.data_ptr(), _fused._stream(dev))
+        return None, None, None, None, None, None, None, dyhat, None
+
+
+def energy_head(yhat: torch.Tensor, y: torch.Tensor, n_samples: int, batch: int, block: str = "joint",
+                fair: bool = False):
+    """``train_functions.energy_loss`` (the definition at ude_energy_forward in include/ude_rk4.h) of y_pred =
+    y_hat (T, S*B, R) as lib/VAE.py:138 reshapes it, against targets y (B, T, R): a scalar that carries autograd
+    to ``yhat`` -- the decoder epilogue's output or any other fp32 HIP tensor of that shape.  On the gfx950
+    energy kernels (no model: any library); more than 128 samples, or more than 1024 times or regions, take
+    the torch definition on the device."""
+    from . import forecast as _forecast
+    import lib.train_functions as train_functions
+    if yhat.dim() != 3:
+        raise ValueError(f"energy_head: y_hat {tuple(yhat.shape)} is not (T, S*B, R)")
+    blocks = train_functions.ENERGY_BLOCKS
+    if block not in blocks:
+        raise ValueError(f"energy_head: block {block!r} is not one of {blocks}")
+    T, N, R = (int(v) for v in yhat.shape)
+    S, B = int(n_samples), int(batch)
+    if N != S * B or tuple(y.shape) != (B, T, R) or S < 1:
+        raise ValueError(f"energy_head: y_hat {tuple(yhat.shape)} / targets {tuple(y.shape)} do not match "
+                         f"S={n_samples}, B={batch}")
+    if fair and S < 2:
+        raise ValueError("energy_head: the fair score needs at least 2 samples")
+    if not yhat.is_cuda or yhat.dtype != torch.float32:
+        raise ValueError("energy_head: y_hat is an fp32 tensor on a HIP device (train_functions.energy_loss "
+                         "is the definition for any other)")
+    lib = _forecast._library()
+    if lib is None:
+        raise _native.UdeError("energy_head: no gfx950 library is built (run __graft_entry__.build())")
+    kind = blocks.index(block)
+    if not lib.energy_supported(T, S, B, R, kind):
+        # beyond the kernels' sizes (the library says which: ude_energy_workspace returns UDE_E_INVALID)
+        return train_functions.energy_loss(yhat.reshape(T, S, B, R).permute(2, 1, 0, 3), y.to(torch.float32),
+                                           block=block, fair=fair)
+    with torch.cuda.device(yhat.device):
+        return _EnergyHead.apply(lib, T, S, B, R, kind, int(bool(fair)), yhat,
+                                 y.to(device=yhat.device, dtype=torch.float32))
 
 
 def nll_head(ode, yhat: torch.Tensor, y: torch.Tensor, n_samples: int, batch: int):

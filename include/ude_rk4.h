@@ -355,6 +355,51 @@ int ude_crps_forward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, c
 int ude_crps_backward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t fair, const float* grad, const void* ws,
                       float* dyhat, ude_stream_t stream);
 
+/* ude_energy_*: the energy-score training head -- the energy score of the ensemble's trajectories against the
+ * observed one, as a differentiable loss: the joint score ude_forecast_joint reports, where ude_crps_* is the
+ * marginal one.  This is the one definition the kernels (csrc/ude_energy.h), lib/train_functions.py energy_loss
+ * and the tests share.
+ *   y_hat (T, S*B, R) fp32, sample n = s*B + b (no model, any y_hat: the decoder epilogue's or another); targets
+ *   y (B, T, R) fp32 in model units (no scaler); y[b,t,r] == -1 means missing, as in nll_loss and crps_loss.
+ *   A block C is a set of coordinates (t, r) of one window b, chosen by `block`; K blocks per window:
+ *     UDE_ENERGY_JOINT  (0): all T R coordinates, K = 1;
+ *     UDE_ENERGY_SERIES (1): region r's T times, K = R;
+ *     UDE_ENERGY_FIELD  (2): the R regions at time t, K = T.
+ *   A coordinate whose target is missing is dropped from its window's blocks, in both terms of the score.
+ *   |.|_C is the Euclidean norm over the live coordinates of C, x_i the row of sample i (x_ic = y_hat[t, i*B+b,
+ *   r]), D = S, or D = S - 1 with fair (S >= 2):
+ *     ES_C          = (1 / S) sum_i |x_i - y|_C - (1 / (2 S D)) sum_i sum_j |x_i - x_j|_C
+ *     loss          = (1 / (B K)) sum_b sum_C ES_C
+ *     d loss / d x_ic = (g / (B K)) [ (x_ic - y_c) / (S |x_i - y|_C) - (1 / (S D)) sum_j (x_ic - x_jc) / |x_i - x_j|_C ]
+ *                     for c live in C.
+ *   A block with no live coordinate contributes 0 and still counts in the divisor B K (nll_loss's convention).  A
+ *   term whose norm is exactly 0 contributes 0 (j = i, tied samples, a sample on the target): the symmetric
+ *   subgradient.  The gradient at a dropped coordinate is exactly 0.  With S = 1 the pair term is exactly 0.
+ *   With D = S and nothing missing the joint / series / field loss is the mean over the windows of
+ *   ude_forecast_joint's energy_joint / energy_series / energy_field; with R = 1 field, and with T = 1 series,
+ *   is ude_crps_forward's loss.
+ *   Arithmetic: differences are formed directly in fp64 after the fp32 load -- never |x_i|^2 + |x_j|^2 - 2 x_i .
+ *   x_j, nor x_ic sum_j w_ij - sum_j w_ij x_jc, which cancel the digits that close members leave; squares are
+ *   summed r ascending within t ascending, one root per pair and block; out[0] and d y_hat are fp32, each
+ *   rounded once from fp64.  Fixed-order sums, no atomics: the same bits run to run.
+ * ude_energy_forward writes out[0] = loss; ws (ude_energy_workspace() bytes, 8-byte aligned: fp64 partials)
+ * is scratch of that call alone.  ude_energy_backward keeps nothing from the forward: given y_hat, y and grad
+ * (device float, d loss / d energy) it forms the pair distances again and writes every element of d y_hat
+ * (T, S*B, R) once.  Stream-ordered, caller-owned buffers, no host read.  1 <= S <= 128, S >= 2 with fair,
+ * T <= 1024, R <= 1024, B <= 65535, block 0..2, no null pointer; UDE_E_INVALID otherwise, before any launch.
+ * The reference has no counterpart: it trains on nll_loss alone. */
+#define UDE_ENERGY_JOINT 0
+#define UDE_ENERGY_SERIES 1
+#define UDE_ENERGY_FIELD 2
+
+int ude_energy_workspace(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int64_t* ws_bytes);
+
+int ude_energy_forward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int32_t fair, const float* yhat,
+                       const float* y, void* ws, float* out, ude_stream_t stream);
+
+int ude_energy_backward(int32_t T, int32_t S, int32_t B, int32_t R, int32_t block, int32_t fair, const float* yhat,
+                        const float* y, const float* grad, float* dyhat, ude_stream_t stream);
+
 /* ---- odeint_adjoint's augmented dynamics (torchdiffeq adjoint; the solver API lib/VAE.py:5 imports) --
  * One evaluation of the right-hand side and its VJP in ONE launch: f_out = f_scale * f(x) (N, R, L),
  * dx = cot_f^T df/dx (N, R, L) and dparams = cot_f^T df/dtheta (torch parameter order).  The reversed
